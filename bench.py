@@ -14,7 +14,12 @@ step is outside the metric and reported beside it: ``with
 followed by clip_grad_norm_(1.0) + AdamW.step() (the reference's update, My_cross_attention.py:831-844) with one re-cast
 of the bf16 weight shadow per step, measured over a bounded number of steps after the timed region.
 
-Rank 0 prints ONE JSON line with the contract's keys plus
+A plain run sets up, warms up, times exactly --steps steps, writes the outputs of the last timed step if --dump-outputs DIR
+is given, and prints the result line; the side legs below and the optimizer leg are null in it.  --full adds everything
+else this file measures: the block of --steps steps timed --repeats times (default 5), the eager / wrapped-module /
+host-input / optimizer legs, c4 in pure bf16, the shadow-cast cost, the roofline and the CPU baseline.
+
+Rank 0 prints ONE JSON line with the contract's keys plus (--full)
   roofline      -- the dominant kernel class (the MFMA GEMMs: >= 97 % of algorithmic FLOPs): algorithmic FLOPs of the
                    GEMM launches of one step / their duration, measured live after the timed region: the launches of one
                    step are recorded and re-issued back to back between ONE pair of HIP events on the launch stream;
@@ -160,6 +165,29 @@ def cpu_baseline(args, fl_sample):
                          args.seq, args.regions, args.cpu_iters, cores)}
 
 
+DUMP_BUDGET = 8 << 20   # float32 elements written by --dump-outputs in all (32 MB)
+
+
+def dump_outputs(path, loss, model):
+    """--dump-outputs: what a caller of the timed step holds after its last call -- the loss and every parameter's gradient
+    -- as float32 files ``loss.npy`` and ``grad.<parameter name>.npy``.  A gradient larger than its share of DUMP_BUDGET is
+    written as a fixed sample: the sorted flat indices drawn by numpy.random.default_rng(crc32 of the parameter name), the
+    same in every run and every build at the same arguments."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy())
+    grads = [(n, p.grad) for n, p in model.named_parameters() if p.grad is not None]
+    cap = DUMP_BUDGET // max(1, len(grads))
+    for name, g in grads:
+        flat = g.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, "grad.%s.npy" % name), flat.float().cpu().numpy())
+    log("outputs of the last timed step: loss + %d gradients -> %s" % (len(grads), path))
+
+
 def _free_port() -> int:
     import socket
     s = socket.socket()
@@ -285,10 +313,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the block of --steps timed steps is run this many times back to back (same graph, same batch pool, each "
                          "block bracketed by barrier + synchronize and reduced by MAX over ranks); value / ms_per_step come from "
-                         "the MEDIAN block, ms_per_step_min / _max give the run's own spread")
+                         "the MEDIAN block, ms_per_step_min / _max give the run's own spread (default: 5 with --full, else 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: --repeats 5, the eager / wrapped-module / host-input / optimizer "
+                         "legs, c4 in pure bf16, the shadow-cast cost, the roofline and the CPU baseline (each can be left out "
+                         "with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and the parameter gradients of the last timed step to DIR/*.npy (float32; large "
+                         "gradients as a fixed sample, see dump_outputs)")
     ap.add_argument("--config", choices=sorted(PRESETS), default=None,
                     help="BASELINE.json configuration preset (default: c2, the configuration the metric is quoted on); "
                          "explicit shape flags override the preset")
@@ -326,7 +361,7 @@ def main():
     ap.add_argument("--dp-diag", default="", help="DIAGNOSTIC: GradReducer(diag=...) -- 'none', 'cast', 'comm', 'cast,comm': "
                                                   "prices parts of the exchange, the gradients are wrong")
     ap.add_argument("--with-optimizer", action="store_true", help="(kept for round-1/2 command lines; the optimizer leg "
-                                                                  "now always runs unless --no-optimizer-leg)")
+                                                                  "runs with --full unless --no-optimizer-leg)")
     ap.add_argument("--no-optimizer-leg", action="store_true", help="skip the fwd+bwd+clip+AdamW leg")
     ap.add_argument("--accumulate", type=int, default=1,
                     help="micro-batches per gradient exchange / zero_grad (the reference's gradient_accumulation_steps, "
@@ -356,6 +391,10 @@ def main():
             setattr(args, k, v)
     if args.precision is None:
         args.precision = "bf16"
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, the outputs and the result line only
+        args.no_eager_leg = args.no_optimizer_leg = args.no_roofline = args.no_cpu_baseline = True
 
     # stdout carries exactly ONE line (the JSON).  Native libraries write there too -- RCCL prints a five-line version banner
     # to fd 1 when its first communicator is created -- so fd 1 is pointed at stderr for the whole run and the JSON line is
@@ -502,6 +541,8 @@ def main():
     final_loss = float(step_loss.item())
     log("%.3f ms/step (median of %d blocks: %s), %.1f samples/s, loss %.4f"
         % (ms_per_step, repeats, " ".join("%.3f" % m for m in ms_blocks), samples_per_s, final_loss))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_loss, model)
 
     # ---- what the import swap of INTEGRATION.md section 1 costs WITHOUT the capture harness: the same step launched eagerly
     #      from Python (autograd + ctypes launches), bounded steps; and what the per-call input refresh of the harness costs
@@ -548,7 +589,7 @@ def main():
                 if getattr(run_step, "nonce", None) is not None:   # the timed step's dropout nonce is the registered one again,
                     K.set_dropout_nonce(run_step.nonce)            # also when this side leg failed half-way
         static = getattr(run_step, "inputs", None)
-        if static is not None:
+        if static is not None and args.full:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             static.refresh(pool[1], {})
             torch.cuda.synchronize()
@@ -634,14 +675,16 @@ def main():
                 K.set_dropout_nonce(run_step.nonce)
 
     # what the default ("always") shadow policy adds to a step: one f32 -> bf16 cast of the GEMM weights
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    arena.sync(force=True)
-    e0.record()
-    for _ in range(10):
+    shadow_cast_us = None
+    if args.full:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         arena.sync(force=True)
-    e1.record()
-    torch.cuda.synchronize()
-    shadow_cast_us = 100.0 * e0.elapsed_time(e1)
+        e0.record()
+        for _ in range(10):
+            arena.sync(force=True)
+        e1.record()
+        torch.cuda.synchronize()
+        shadow_cast_us = 100.0 * e0.elapsed_time(e1)
 
     # ---- the optimizer beside the metric: the same step + clip_grad_norm_(1.0) + AdamW.step(), as the
     #      reference's loop does after backward (My_cross_attention.py:831-844).  Every optimizer step is seen by the arena
@@ -776,7 +819,8 @@ def main():
             "value": round(samples_per_s, 2), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             # the run's own noise bar: `repeats` blocks of `steps` steps each, value / ms_per_step from the MEDIAN block
-            "repeats": repeats, "ms_per_step_min": round(min(ms_blocks), 3), "ms_per_step_max": round(max(ms_blocks), 3),
+            "repeats": repeats, "ms_per_step_min": round(1e3 * min(blocks) / args.steps, 3),
+            "ms_per_step_max": round(1e3 * max(blocks) / args.steps, 3),
             "ms_per_step_blocks": ms_blocks,
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None,
@@ -796,7 +840,7 @@ def main():
                        % ("bf16" if reducer.comm_bf16 else "f32", len(reducer.buckets), reducer.backend,
                           reducer.wire_bytes() >> 20, (" DIAG=" + args.dp_diag) if args.dp_diag else "") +
                        ("" if reducer.sparse_word is None else "; word-embedding gradient as all-gathered token rows")},
-            "shadow_cast_us": round(shadow_cast_us, 1),
+            "shadow_cast_us": None if shadow_cast_us is None else round(shadow_cast_us, 1),
             # the same step without the capture harness (eager launches from Python: what a plain import swap of the
             # reference's modules gets), and the per-call copy of a new batch into the captured step's static input buffers
             # (inside the timed region: every timed step is fed another batch)

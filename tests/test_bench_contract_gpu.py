@@ -1,5 +1,5 @@
-"""GPU: the contract of `python bench.py` at N = 1 (what the driver runs at the end of a round): stdout carries exactly ONE JSON
-line with the metric / unit / config BASELINE.json names, whole-job throughput consistent with ms_per_step, the `roofline` object
+"""GPU: the contract of `python bench.py --full` at N = 1 (what the driver runs at the end of a round): stdout carries exactly
+ONE JSON line with the metric / unit / config BASELINE.json names, whole-job throughput consistent with ms_per_step, the `roofline` object
 (MFMA bound, achieved / peak / frac consistent, per-launch algorithmic bytes and flops, the committed PMC traffic and MFMA-busy
 figures for c2) and the `cpu_baseline` object (the oracle timed on the host cores, bounded sample), plus the side legs this repo
 reports beside the headline (eager launches, the wrapped module, host-resident inputs, the optimizer)."""
@@ -19,8 +19,8 @@ def test_default_bench_line_keeps_the_contract():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--cpu-iters", "1",
-                        "--optimizer-steps", "5", "--eager-steps", "5"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5",
+                        "--cpu-iters", "1", "--optimizer-steps", "5", "--eager-steps", "5"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     err = p.stderr.decode("utf-8", "replace")
     assert p.returncode == 0, err[-4000:]
@@ -66,3 +66,38 @@ def test_default_bench_line_keeps_the_contract():
     # (timing RELATIONS between the side legs are reported, not asserted: short legs on a shared box jitter)
     print("\n[bench contract] %.3f ms/step = %.0f samples/s; GEMM class %.3f of the bf16 roof; CPU oracle %.1f samples/s on %d threads"
           % (d["ms_per_step"], d["value"], r["frac"], c["value"], c["cores"]))
+
+
+def test_plain_bench_line_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): ONE block of exactly --steps timed steps, the headline keys as above, no side legs; with
+    --dump-outputs the loss and the parameter gradients of the last timed step as float32 .npy files, 64 MB at most."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out_dir = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3",
+                        "--dump-outputs", str(out_dir)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600)
+    err = p.stderr.decode("utf-8", "replace")
+    assert p.returncode == 0, err[-4000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("MNER samples/sec (fwd+bwd) at seq=128, 36 regions, bs=32") and d["unit"] == "samples/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16" and d["config"]["launch"] == "hipgraph"
+    assert d["steps"] == 10 and d["warmup"] == 3 and d["repeats"] == 1 and len(d["ms_per_step_blocks"]) == 1
+    assert "timing 1 x 10 steps" in err
+    assert d["value"] == pytest.approx(32 / (d["ms_per_step"] * 1e-3), rel=1e-3) and 1.0 < d["ms_per_step"] < 50.0
+    for k in ("roofline", "cpu_baseline", "eager_ms_per_step", "wrapped_module_ms_per_step", "host_inputs_ms_per_step",
+              "refresh_us", "shadow_cast_us"):
+        assert d[k] is None, k
+    assert "with_optimizer_ms_per_step" not in d and "config_as_stated" not in d
+    files = sorted(os.listdir(out_dir))
+    assert "loss.npy" in files and len([f for f in files if f.startswith("grad.")]) > 200
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 << 20
+    loss = np.load(out_dir / "loss.npy")
+    assert loss.dtype == np.float32 and float(loss) == pytest.approx(d["loss"], abs=1e-5)
+    grads = [np.load(out_dir / f) for f in files if f.startswith("grad.")]
+    assert all(g.dtype == np.float32 and g.ndim == 1 and np.isfinite(g).all() for g in grads)
+    assert sum(int(np.count_nonzero(g)) for g in grads) > 0

@@ -23,7 +23,7 @@ def test_bench_gpus_n_launches_its_own_ranks(n):
     env = dict(os.environ, ICKA_BENCH_BACKEND="gloo", ICKA_BENCH_ONE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full", "--steps", "3", "--warmup", "1",
                         "--no-cpu-baseline", "--no-roofline", "--optimizer-steps", "2", "--eager-steps", "2", "--eager-leg-dist"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600)
     err = p.stderr.decode("utf-8", "replace")
