@@ -39,6 +39,7 @@ ROCm devices and with ``gloo`` (CPU tensors; device tensors are staged through t
 """
 from __future__ import annotations
 
+import contextlib
 import sys
 from typing import Dict, List, Optional, Tuple
 
@@ -94,12 +95,15 @@ class CaptureDisagreement(RuntimeError):
     succeeded): the ranks take the same fallback together."""
 
 
-class _NullCtx(object):
-    def __enter__(self):
-        return self
+class CapturedRows(object):
+    """What the embedding backward of a captured step left for the row-sparse word-table exchange (``GradReducer.capturing``):
+    ``args`` = the ``(rows, ids, accumulate)`` it registered through ``set_sparse_rows`` -- static buffers that every replay
+    fills -- or None (no rows: the fp32-exact mode writes the table densely); ``word_written`` = the table's slot received a
+    gradient write."""
 
-    def __exit__(self, *a):
-        return False
+    def __init__(self):
+        self.args = None
+        self.word_written = False
 
 # CUs dp.GradReducer keeps free of persistent BiLSTM blocks while RCCL workgroups may share the GPU (icka_hip.h:
 # icka_lstm_set_reserved_cus): RCCL runs one workgroup per channel, at most 64 channels
@@ -178,10 +182,9 @@ class GradReducer(object):
         self._seen: Dict[int, int] = {}
         self._waiting = [0] * len(self.buckets)   # per bucket: slots that have not received all their writes yet
         self._launched = [False] * len(self.buckets)
-        # graph capture (graph.SegmentedStep / graph.FlaggedStep): while ``capture`` is set, a bucket that becomes ready is
-        # not launched but reported to it (``bucket_ready(idx)``, then ``after_mark()`` once per mark_final call)
+        # graph capture: the protocol of ``capturing`` and the state of ``mute`` (graph.py drives both through those methods)
         self.capture = None
-        self.muted = False       # graph.FlaggedStep, captures of the micro-batches that do not exchange: finish() is a no-op
+        self.muted = False
         # ---- bf16 wire buffer (module docstring)
         self.gwire = None
         self._wire_ranges = set()                 # (offset, numel) of gradients whose wire copy a GEMM epilogue writes
@@ -204,9 +207,11 @@ class GradReducer(object):
 
     def abort_step(self) -> None:
         """Forget the step in flight (a capture or an eager step that raised half-way): no bucket is marked launched, no
-        write counted, no rows pending, no capture protocol attached.  The calibration is kept."""
+        write counted, no rows pending, no capture protocol attached, not muted, attached to the arena again.  The calibration
+        is kept."""
         self.capture = None
         self.muted = False
+        self.arena.reducer = self
         self._sparse = None
         self._word_written = False
         self._seen = {}
@@ -214,6 +219,43 @@ class GradReducer(object):
         for sid in self._expected:
             self._waiting[self._bucket_of[sid]] += 1
         self._launched = [False] * len(self.buckets)
+
+    # ------------------------------------------------------------------------------------------------- graph capture
+    @contextlib.contextmanager
+    def capturing(self, protocol):
+        """For the duration of a hipGraph capture of the step (graph.SegmentedStep's cuts, the flag nodes of graph.FlaggedStep
+        and GraphedModule): a bucket that becomes ready is not launched but reported to ``protocol`` (``bucket_ready(idx)``,
+        then ``after_mark()`` once per mark_final call), and ``finish`` reports the remaining buckets without exchanging or
+        joining.  Yields a ``CapturedRows``, filled on exit with what the captured embedding backward left for the row-sparse
+        exchange (taken out of the step state: a replay hands it back, ``set_sparse_rows`` / ``exchange_sparse``)."""
+        taken = CapturedRows()
+        self.capture = protocol
+        try:
+            yield taken
+        finally:
+            self.capture = None
+            taken.args, taken.word_written = self._sparse, self._word_written
+            self._sparse, self._word_written = None, False
+
+    def mute(self) -> None:
+        """Detach from the arena and make ``finish`` return at once: a backward that must not exchange (no wire copies, no
+        flags, no bucket state moves): in graph.py, the micro-batches of an accumulation cycle before its last one and the
+        compute-only capture.  ``unmute`` undoes it."""
+        self.arena.reducer = None
+        self.muted = True
+
+    def unmute(self) -> None:
+        self.arena.reducer = self
+        self.muted = False
+
+    @contextlib.contextmanager
+    def muted_detached(self):
+        """``mute`` for the body, ``unmute`` after it (also when it raises)."""
+        self.mute()
+        try:
+            yield
+        finally:
+            self.unmute()
 
     def close(self) -> None:
         """Detach from the arena and give back the CU reservation taken for the persistent BiLSTM kernels."""
@@ -493,17 +535,16 @@ class GradReducer(object):
             self._sparse_ws[key] = ws
         return ws
 
-    def _exchange_word_dense(self) -> None:
+    def _exchange_word_dense(self, after_current: bool) -> None:
         """The word table's slot was written DENSELY in this step (an embedding backward that does not know the row path: the
         fp32-exact mode, the prompt embeddings of cross_modal): mean all-reduce of the slot, like any bucket."""
         w = self.sparse_word
         g = self.arena.gflat[w.off:w.off + w.numel]
         self.sparse_stats["dense_slot"] = self.sparse_stats.get("dense_slot", 0) + 1
         if self.is_cuda and self.backend == "nccl":
-            on_current = getattr(self, "_exchange_on_current", False)
-            if not on_current:
+            if after_current:
                 self.comm_stream.wait_stream(torch.cuda.current_stream())
-            with (_NullCtx() if on_current else torch.cuda.stream(self.comm_stream)):
+            with torch.cuda.stream(self.comm_stream):
                 dist.all_reduce(g, op=dist.ReduceOp.AVG, group=self.group)
             return
         host = g.cpu() if self.is_cuda else g
@@ -512,22 +553,24 @@ class GradReducer(object):
         if self.is_cuda:
             g.copy_(host)
 
-    def exchange_sparse(self, word_written: Optional[bool] = None) -> None:
+    def exchange_sparse(self, word_written: Optional[bool] = None, after_current: bool = True) -> None:
         """All-gather every rank's token rows + ids and add (1 / world) * rows into the word table's gradient slot; dense
         fallback (local scatter + all-reduce of the slot) when a rank brings at least vocab / 4 rows.  On devices with RCCL the
-        work goes to the communication stream (after everything already on the current stream); ``join`` orders it before the
-        consumers of the gradient.  A step whose embedding backward registered NO rows but wrote the slot densely
-        (``word_written``; default: what ``mark_final`` saw in the step in flight) gets a plain mean all-reduce of the slot, so
-        no path leaves the replicas with local word gradients.  The row count T and with it the path (rows / dense) and the
-        all-gather sizes are agreed across the ranks the first time each T is seen (host-side, over the store): ragged counts
-        raise on every rank instead of pairing an all-reduce with an all-gather."""
+        work goes to the communication stream, after everything already on the current stream -- with ``after_current=False``
+        only after what the communication stream already holds (graph.FlaggedStep: behind the last bucket's flag wait, while
+        the current stream holds the whole replayed step); ``join`` orders it before the consumers of the gradient.  A step
+        whose embedding backward registered NO rows but wrote the slot densely (``word_written``; default: what ``mark_final``
+        saw in the step in flight) gets a plain mean all-reduce of the slot, so no path leaves the replicas with local word
+        gradients.  The row count T and with it the path (rows / dense) and the all-gather sizes are agreed across the ranks
+        the first time each T is seen (host-side, over the store): ragged counts raise on every rank instead of pairing an
+        all-reduce with an all-gather."""
         if self.sparse_word is None:
             return
         written = self._word_written if word_written is None else bool(word_written)
         self._word_written = False
         if self._sparse is None:
             if written:
-                self._exchange_word_dense()
+                self._exchange_word_dense(after_current)
             return
         rows, ids, accumulate = self._sparse
         self._sparse = None
@@ -563,11 +606,9 @@ class GradReducer(object):
             return
         from . import kernels as K
         nccl = self.backend == "nccl"
-        on_current = getattr(self, "_exchange_on_current", False)     # graph.FlaggedStep: already on the communication stream
-        if nccl and not on_current:
+        if nccl and after_current:
             self.comm_stream.wait_stream(torch.cuda.current_stream())
-        ctx = torch.cuda.stream(self.comm_stream) if (nccl and not on_current) else _NullCtx()
-        with ctx:
+        with (torch.cuda.stream(self.comm_stream) if nccl else contextlib.nullcontext()):
             if dense:
                 if accumulate:
                     tmp = self.arena.workspace("sparse_dense", V * H).view(V, H)

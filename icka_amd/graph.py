@@ -54,6 +54,7 @@ and take the next form together.  ``build_step`` is that chain (flagged -> segme
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import sys
 from typing import Callable, Optional
@@ -263,7 +264,10 @@ class DevicePrefetcher(object):
 
 
 class _StepBase(object):
-    """Shared by the step objects: the dropout nonce, the static inputs, warm-up, and which capture a call replays."""
+    """Shared by the step objects: the dropout nonce, the static inputs, warm-up, the replay preamble, and which capture a call
+    replays.  ``_name``: the wrapper's name in the errors it raises."""
+
+    _name = ""
 
     def _setup(self, model, step_fn, inputs, nonce=None):
         dev = next(model.parameters()).device
@@ -276,6 +280,7 @@ class _StepBase(object):
         self.nonce = torch.zeros(2, dtype=torch.int32, device=dev) if nonce is None else nonce
         K.set_dropout_nonce(self.nonce)
         self.side = torch.cuda.Stream(device=dev)
+        self._detected = "detected before a %s replay" % self._name
 
     def _step(self):
         return self.inputs.call(self._user_fn) if self.inputs is not None else self._user_fn()
@@ -290,11 +295,29 @@ class _StepBase(object):
         torch.cuda.current_stream().wait_stream(self.side)
         torch.cuda.synchronize()
 
-    def _refresh(self, args, kwargs):
-        if args or kwargs:
-            if self.inputs is None:
-                raise TypeError("this step was built without inputs=: it replays a closure over fixed tensors")
-            self.inputs.refresh(args, kwargs)
+    def _values(self, args, kwargs):
+        """A call's inputs in the order of the static buffers; None for a call without any (replay on the buffers as they are)."""
+        if not (args or kwargs):
+            return None
+        if self.inputs is None:
+            raise TypeError("this step was built without inputs=: it replays a closure over fixed tensors")
+        return self.inputs.values_of(args, kwargs)
+
+    def _prepare(self, closed: bool, values, flags: bool = False) -> None:
+        """What comes before every replay: refuse a closed wrapper, copy ``values`` (None: none) into the static inputs,
+        refresh the bf16 shadow unless the captured forward casts it (policy "always"), and raise what a launch of an EARLIER
+        replay left in a host-mapped error word -- a persistent LSTM or fused dense + LayerNorm launch that gave up a hand-off
+        (NaN-poisoned outputs) and, with ``flags``, a bucket-ready flag wait that gave up (host reads, no synchronisation)."""
+        if closed:
+            raise RuntimeError("%s is closed" % self._name)
+        if values is not None:
+            self.inputs.refresh_values(values)
+        if self.arena.shadow_policy != "always":
+            self.arena.sync()
+        K.lstm_check_error(self._detected)
+        K.gemm_ln_check_error(self._detected)
+        if flags:
+            K.dp_check_error(self._detected)
 
     def _cycle_state(self):
         """(accumulate, stale): accumulate = some gradient of this step is still held by the caller (ParamArena._is_live:
@@ -312,16 +335,21 @@ class _StepBase(object):
             A.gflat[s.off:s.off + s.numel].zero_()
 
     def _close_nonce(self):
-        if getattr(self, "nonce", None) is not None:
-            if getattr(self, "_owns_nonce", True):
-                try:
-                    K.clear_dropout_nonce_if(self.nonce)
-                except Exception:      # interpreter shutdown: the library may already be gone
-                    pass
-            self.nonce = None
+        if getattr(self, "_owns_nonce", True):
+            _release_nonce(getattr(self, "nonce", None))
+        self.nonce = None
 
     def __del__(self):
         self.close()
+
+
+def _release_nonce(nonce) -> None:
+    """Unregister a dropout nonce (the kernels keep a raw pointer to it); None: nothing to do."""
+    if nonce is not None:
+        try:
+            K.clear_dropout_nonce_if(nonce)
+        except Exception:      # interpreter shutdown: the library may already be gone
+            pass
 
 
 def _end_capture_quietly() -> None:
@@ -332,9 +360,48 @@ def _end_capture_quietly() -> None:
         pass
 
 
+def _agreed(reducer, err, what: str) -> bool:
+    """The vote that ends the capture phase of a data-parallel form (module docstring): True iff the capture worked on every
+    rank -- on this one iff ``err`` is None.  Otherwise this rank's step in flight is forgotten (``GradReducer.abort_step``;
+    the reducer stays attached) and the caller takes its fallback, as every other rank does."""
+    from .dp import all_ranks_agree
+    if all_ranks_agree(err is None, reducer.group, what):
+        return True
+    reducer.abort_step()
+    return False
+
+
+def _disagreement(who: str, what: str, err):
+    """The ``dp.CaptureDisagreement`` every rank raises after a lost vote; ``err``: this rank's own capture error, or None."""
+    from .dp import CaptureDisagreement
+    if err is None:
+        return CaptureDisagreement("%s: another rank could not capture %s" % (who, what))
+    return CaptureDisagreement("%s: this rank could not capture %s (%s: %s)" % (who, what, type(err).__name__, err))
+
+
+class _Cycle(object):
+    """Position in an accumulation cycle of ``k`` micro-batches: only the k-th call exchanges the gradients, and a cycle
+    restarts whenever the caller dropped them (``zero_grad``) before that."""
+
+    def __init__(self, k: int):
+        self.k = k
+        self.micro = 0
+
+    def exchanges(self, held: bool) -> bool:
+        """Does this call exchange?  ``held``: the caller still holds gradients written earlier in this cycle."""
+        if not held:
+            self.micro = 0                      # the caller dropped the gradients: a new cycle starts here
+        return self.micro == self.k - 1
+
+    def done(self, exchanged: bool) -> None:
+        self.micro = 0 if exchanged else self.micro + 1
+
+
 class _StepCapture(_StepBase):
     """ONE captured forward + backward step at fixed input shapes and one train / eval mode: an overwrite graph and (lazily) an
     accumulate graph.  ``GraphedStep`` keeps a cache of these."""
+
+    _name = "GraphedStep"
 
     def __init__(self, model, step_fn, warmup=3, inputs=None, nonce=None):
         self._setup(model, step_fn, inputs, nonce)
@@ -372,16 +439,7 @@ class _StepCapture(_StepBase):
     def run(self, values=None) -> torch.Tensor:
         """Refresh the static inputs with ``values`` (already in buffer order; None = replay on the buffers as they are), pick
         the overwrite or the accumulate capture, replay."""
-        if self._graphs is None:
-            raise RuntimeError("GraphedStep is closed")
-        if values is not None:
-            self.inputs.refresh_values(values)
-        if self.arena.shadow_policy != "always":   # "always": the cast is a node of the captured forward
-            self.arena.sync()
-        # a persistent LSTM launch of an EARLIER replay that gave up a hand-off (NaN-poisoned outputs): raise at this host
-        # touch-point (a host read of a mapped word, no synchronisation)
-        K.lstm_check_error("detected before a GraphedStep replay")
-        K.gemm_ln_check_error("detected before a GraphedStep replay")
+        self._prepare(self._graphs is None, values)
         accumulate, stale = self._cycle_state()
         if accumulate and True not in self._graphs:
             self._capture(True)                 # (a capture executes nothing: the gradients held so far are untouched)
@@ -392,11 +450,7 @@ class _StepCapture(_StepBase):
         return self.loss
 
     def __call__(self, *args, **kwargs) -> torch.Tensor:
-        if args or kwargs:
-            if self.inputs is None:
-                raise TypeError("this step was built without inputs=: it replays a closure over fixed tensors")
-            return self.run(self.inputs.values_of(args, kwargs))
-        return self.run(None)
+        return self.run(self._values(args, kwargs))
 
     def close(self) -> None:
         """Release the graphs and unregister the dropout nonce (the kernels keep a raw pointer to it)."""
@@ -522,12 +576,8 @@ class GraphedStep(object):
             for c in self._caps.values():
                 c.close()
         self._caps = None
-        if self.nonce is not None:
-            try:
-                K.clear_dropout_nonce_if(self.nonce)
-            except Exception:      # interpreter shutdown
-                pass
-            self.nonce = None
+        _release_nonce(self.nonce)
+        self.nonce = None
 
     def __del__(self):
         try:
@@ -558,6 +608,8 @@ class _ModuleCapture(_StepBase):
     """ONE captured call of a module at a fixed call signature, input shapes, train / eval mode and grad mode: a forward graph
     and -- when the output requires grad -- the backward graphs (overwrite / accumulate, with / without the gradient exchange).
     ``GraphedModule`` keeps a cache of these."""
+
+    _name = "GraphedModule"
 
     def __init__(self, owner, args, kwkeys, kwvalues, warmup):
         self.owner = owner
@@ -603,7 +655,7 @@ class _ModuleCapture(_StepBase):
             if reducer.arena is not self.arena:
                 raise ValueError("GraphedModule(reducer=): the reducer belongs to another model's arena")
             self.arena.reducer = reducer
-            self._xch = _FlagExchange(reducer, self.arena, self.device)
+            self._xch = _FlagExchange(reducer)
         # ---- the capture phase proper: no process-group traffic from here on (the exchanging backward captures carry flag
         #      nodes only), so it may fail on one rank alone -- GraphedModule votes afterwards
         model.zero_grad()
@@ -632,7 +684,6 @@ class _ModuleCapture(_StepBase):
             self.gf, self._bwd = None, {}
             if reducer is not None:
                 reducer.abort_step()
-                self.arena.reducer = reducer
             self.arena.keep_saved = False
             _end_capture_quietly()
             raise
@@ -657,24 +708,17 @@ class _ModuleCapture(_StepBase):
             raise RuntimeError("this GraphedModule call was captured without a backward (its output did not require grad)")
         self.gout.copy_(g.expand_as(self.gout) if g.shape != self.gout.shape else g, non_blocking=True)
         accumulate, stale = self._cycle_state()
-        exchange = False
-        owner = self.owner
-        if self.reducer is not None:
-            if not accumulate:
-                owner._micro = 0                # the caller dropped the gradients: a new cycle starts here
-            exchange = owner._micro == self.accumulate - 1
+        cycle = self.owner._cycle               # None without a reducer: nothing is exchanged
+        exchange = cycle is not None and cycle.exchanges(accumulate)
         key = (accumulate, exchange)
         if key not in self._bwd:                # (accumulate = k > 1 and the first backward of a cycle is also its last: k == 1 only)
             raise RuntimeError("GraphedModule: no backward capture for accumulate=%s, exchange=%s" % key)
         self._zero(stale)
-        if exchange:
-            self._xch.before_replay()
         self._bwd[key].replay()
         if exchange:
             self._xch.after_replay(self._order[key])
-            owner._micro = 0
-        elif self.reducer is not None:
-            owner._micro += 1
+        if cycle is not None:
+            cycle.done(exchange)
         self.arena.attach_grads(self._grad_slots)
 
     def _capture_bwd(self, accumulate: bool, exchange: bool) -> None:
@@ -683,50 +727,25 @@ class _ModuleCapture(_StepBase):
             arena.attach_grads(self._grad_slots)
         g = torch.cuda.CUDAGraph()
         key = (accumulate, exchange)
+        graph = torch.cuda.graph(g, pool=self.gf.pool(), capture_error_mode="thread_local")
         arena.keep_saved = True
         try:
             if exchange:
-                cap = _FlagCapture(self._xch.sync)
-                r.capture = cap
-                arena.reducer = r
-                try:
-                    with torch.autograd.set_multithreading_enabled(False), \
-                            torch.cuda.graph(g, pool=self.gf.pool(), capture_error_mode="thread_local"):
-                        self._xch.first_node()
-                        self.out.backward(self.gout, retain_graph=True)
-                        r.finish()              # reports the remaining buckets (their flags rise at the end of the graph)
-                finally:
-                    r.capture = None
-                torch.cuda.synchronize()
-                if sorted(cap.order) != list(range(len(r.buckets))):
-                    raise RuntimeError("GraphedModule: buckets flagged during capture %s != all %d buckets" % (cap.order, len(r.buckets)))
-                self._order[key] = cap.order
+                def backward():
+                    self.out.backward(self.gout, retain_graph=True)
+                    r.finish()                  # reports the remaining buckets (their flags rise at the end of the graph)
+                _, self._order[key], _ = self._xch.capture(graph, backward, "GraphedModule")
             else:
-                if r is not None:               # a backward that does not exchange: reducer detached, no wire copies, no flags
-                    arena.reducer = None
-                    r.muted = True
-                try:
-                    with torch.autograd.set_multithreading_enabled(False), \
-                            torch.cuda.graph(g, pool=self.gf.pool(), capture_error_mode="thread_local"):
-                        self.out.backward(self.gout, retain_graph=True)
-                finally:
-                    if r is not None:
-                        arena.reducer = r
-                        r.muted = False
+                # a backward that does not exchange: reducer detached, no wire copies, no flags
+                with (r.muted_detached() if r is not None else contextlib.nullcontext()), \
+                        torch.autograd.set_multithreading_enabled(False), graph:
+                    self.out.backward(self.gout, retain_graph=True)
         finally:
             arena.keep_saved = False
         self._bwd[key] = g
 
     def run(self, values) -> torch.Tensor:
-        if self.gf is None:
-            raise RuntimeError("GraphedModule is closed")
-        self.inputs.refresh_values(values)
-        if self.arena.shadow_policy != "always":
-            self.arena.sync()
-        K.lstm_check_error("detected before a GraphedModule replay")
-        K.gemm_ln_check_error("detected before a GraphedModule replay")
-        if self.reducer is not None:
-            K.dp_check_error("detected before a GraphedModule replay")
+        self._prepare(self.gf is None, values, flags=self.reducer is not None)
         if torch.is_grad_enabled() and self._bwd:
             return self._fn.apply(self.arena.anchor)
         self.gf.replay()
@@ -794,7 +813,7 @@ class GraphedModule(object):
         d["accumulate"] = int(accumulate)
         d["max_captures"] = int(max_captures)
         d["_warmup"] = warmup
-        d["_micro"] = 0
+        d["_cycle"] = _Cycle(int(accumulate)) if reducer is not None else None
         d["_caps"] = {}
         d["_eager_keys"] = {}
         d["_eager_exchange"] = False
@@ -807,13 +826,9 @@ class GraphedModule(object):
         key = (len(example_args), kwkeys, _sig(values), bool(module.training), torch.is_grad_enabled())
         cap, err = self._build(key, example_args, kwkeys, [example_kwargs[k] for k in kwkeys])
         if cap is None:
-            from .dp import CaptureDisagreement
-            if err is None:
-                raise CaptureDisagreement("GraphedModule: another rank could not capture the example call")
-            if reducer is not None:
-                raise CaptureDisagreement("GraphedModule: this rank could not capture the example call (%s: %s)"
-                                          % (type(err).__name__, err)) from err
-            raise err
+            if reducer is None:
+                raise err
+            raise _disagreement("GraphedModule", "the example call", err) from err
         d["_primary"] = cap
         d["arena"] = cap.arena
 
@@ -860,12 +875,10 @@ class GraphedModule(object):
         finally:
             if snap is not None:
                 snap.restore()
-        if self.reducer is not None and key[4]:
-            from .dp import all_ranks_agree
-            if not all_ranks_agree(cap is not None, self.reducer.group, "GraphedModule capture %s" % (key[:4],)):
-                if cap is not None:
-                    cap.close()
-                cap = None
+        if self.reducer is not None and key[4] and not _agreed(self.reducer, err, "GraphedModule capture %s" % (key[:4],)):
+            if cap is not None:
+                cap.close()
+            cap = None
         if cap is not None:
             self._caps[key] = cap
             self.stats["captures"] += 1
@@ -908,25 +921,19 @@ class GraphedModule(object):
         return _EagerTail.apply(out, self)
 
     def _eager_backward_begins(self) -> None:
-        A, r = self.arena, self.reducer
-        if not any(A._is_live(s) for s in A.order):
-            self._micro = 0                     # the caller dropped the gradients: a new cycle starts here
-        self._eager_exchange = self._micro == self.accumulate - 1
+        A = self.arena
+        self._eager_exchange = self._cycle.exchanges(any(A._is_live(s) for s in A.order))
         if self._eager_exchange:
-            A.reducer = r
+            A.reducer = self.reducer
         else:
-            A.reducer = None
-            r.muted = True
+            self.reducer.mute()
 
     def _eager_backward_ends(self) -> None:
-        A, r = self.arena, self.reducer
         if self._eager_exchange:
-            r.finish()
-            self._micro = 0
+            self.reducer.finish()
         else:
-            A.reducer = r
-            r.muted = False
-            self._micro += 1
+            self.reducer.unmute()
+        self._cycle.done(self._eager_exchange)
 
     def close(self) -> None:
         d = self.__dict__
@@ -934,12 +941,8 @@ class GraphedModule(object):
             for c in d["_caps"].values():
                 c.close()
         d["_caps"] = None
-        if d.get("nonce") is not None:
-            try:
-                K.clear_dropout_nonce_if(d["nonce"])
-            except Exception:      # interpreter shutdown
-                pass
-            d["nonce"] = None
+        _release_nonce(d.get("nonce"))
+        d["nonce"] = None
 
     def __del__(self):
         try:
@@ -996,6 +999,8 @@ class SegmentedStep(_StepBase):
     attached to the model's arena.  ``inputs`` / per-call refresh as ``GraphedStep``; every call overwrites the gradients
     and exchanges them (no accumulation across calls: the fallback form -- ``FlaggedStep`` has ``accumulate=``)."""
 
+    _name = "SegmentedStep"
+
     def __init__(self, model: torch.nn.Module, step_fn: Callable[..., torch.Tensor], reducer, warmup: int = 3, inputs=None):
         self._setup(model, step_fn, inputs)
         self.reducer = reducer
@@ -1006,12 +1011,11 @@ class SegmentedStep(_StepBase):
         model.zero_grad()                       # gradients dropped -> captured kernels overwrite (beta = 0)
         # ---- capture phase: no process-group traffic (a ready bucket cuts the graph), may fail on one rank alone
         cap = _Capture()
-        reducer.capture = cap
         err = None
         try:
             # backward on THIS thread: begin / end of a stream capture must come from one thread, and the cuts happen
             # inside backward (GradReducer.mark_final)
-            with torch.cuda.stream(side), torch.autograd.set_multithreading_enabled(False):
+            with reducer.capturing(cap) as taken, torch.cuda.stream(side), torch.autograd.set_multithreading_enabled(False):
                 cap.begin()
                 try:
                     K.bump_dropout_nonce(self.nonce)
@@ -1027,44 +1031,29 @@ class SegmentedStep(_StepBase):
                     raise
         except Exception as e:  # noqa: BLE001
             err = e
-        finally:
-            reducer.capture = None
         _end_capture_quietly()
         torch.cuda.current_stream().wait_stream(side)
-        from .dp import CaptureDisagreement, all_ranks_agree
-        if not all_ranks_agree(err is None, reducer.group, "SegmentedStep capture"):
-            reducer.abort_step()
-            self.arena.reducer = reducer
+        if not _agreed(reducer, err, "SegmentedStep capture"):
             model.zero_grad()
             self._close_nonce()
-            if err is None:
-                raise CaptureDisagreement("SegmentedStep: another rank could not capture the step")
-            raise CaptureDisagreement("SegmentedStep: this rank could not capture the step (%s: %s)" % (type(err).__name__, err)) from err
+            raise _disagreement("SegmentedStep", "the step", err) from err
         self.segments = cap.segments
         # row-sparse word-table exchange: the static row / id buffers the captured backward fills -- or, when the step's
         # embedding backward wrote the table densely (fp32-exact mode), a dense mean all-reduce of the slot per replay
-        self._sparse_args, self._word_written = None, False
-        if getattr(reducer, "sparse_word", None) is not None:
-            self._sparse_args, reducer._sparse = reducer._sparse, None
-            self._word_written, reducer._word_written = reducer._word_written or self._sparse_args is not None, False
+        self._rows = taken.args
+        self._word_exchange = taken.word_written or taken.args is not None
         self._grad_slots = [s for s in self.arena.order if s.live]
         model.zero_grad()                       # a capture executes nothing: the gradients it "wrote" do not exist
 
     def __call__(self, *args, **kwargs) -> torch.Tensor:
-        if self.segments is None:
-            raise RuntimeError("SegmentedStep is closed")
-        self._refresh(args, kwargs)
-        if self.arena.shadow_policy != "always":
-            self.arena.sync()
-        K.lstm_check_error("detected before a SegmentedStep replay")
-        K.gemm_ln_check_error("detected before a SegmentedStep replay")
+        self._prepare(self.segments is None, self._values(args, kwargs))
         for graph, buckets in self.segments:
             graph.replay()
             for bi in buckets:
                 self.reducer.launch_now(bi)
-        if self._word_written:
-            if self._sparse_args is not None:
-                self.reducer.set_sparse_rows(*self._sparse_args)
+        if self._word_exchange:
+            if self._rows is not None:
+                self.reducer.set_sparse_rows(*self._rows)
             self.reducer.exchange_sparse(word_written=True)
         self.reducer.join()
         self.arena.attach_grads(self._grad_slots)
@@ -1076,16 +1065,16 @@ class SegmentedStep(_StepBase):
 
 
 class _FlagCapture(object):
-    """Capture protocol of ``FlaggedStep``: a bucket that becomes ready while the step is being captured gets a flag-set
-    node in the graph (icka_dp_flag_set on the capturing stream) instead of a collective."""
+    """Capture protocol of the flag-word exchange (``_FlagExchange``): a bucket that becomes ready while the step is being
+    captured gets a flag-set node in the graph (icka_dp_flag_set on the capturing stream) instead of a collective."""
 
     def __init__(self, sync_words: torch.Tensor):
         self.sync = sync_words
         self.order = []
 
     def bucket_ready(self, idx: int) -> None:
-        K.check(K._lib.load().icka_dp_flag_set(self.sync[FlaggedStep.FLAG0 + idx:].data_ptr(), self.sync.data_ptr(), K._stream()),
-                "icka_dp_flag_set")
+        K.check(K._lib.load().icka_dp_flag_set(self.sync[_FlagExchange.FLAG0 + idx:].data_ptr(), self.sync.data_ptr(),
+                                               K._stream()), "icka_dp_flag_set")
         self.order.append(idx)
 
     def after_mark(self) -> None:
@@ -1093,36 +1082,69 @@ class _FlagCapture(object):
 
 
 class _FlagExchange(object):
-    """The replay-side half of the flag-word protocol (``FlaggedStep`` docstring) for a capture that is not a whole step
-    (``GraphedModule``'s backward): the sync words, the tag of the next exchanging replay, and the flag waits + eager all-reduces
-    + join + final poison pass behind a replay."""
+    """The flag-word protocol (``FlaggedStep`` docstring) of a capture that exchanges the gradients -- ``FlaggedStep``'s whole
+    step, ``GraphedModule``'s backward; each takes the capture in its own graph context.  It owns the sync words, the tag of
+    the replay in flight, the capture of the flag nodes (``capture``) and what follows a replay (``after_replay``).
 
-    def __init__(self, reducer, arena, device):
-        import os
+    Sync words: [0] step counter (bumped by the capture's first node), [FLAG0 + i] flag of bucket i, [FLAG0 + nb + i] BAD
+    word of bucket i (the step number of a wait that gave up), [FLAG0 + 2 nb + 8] a word no node ever sets (``test_late``)."""
+
+    FLAG0 = 16
+    WAIT_POLLS = 1 << 20   # ~3 s of s_sleep(64) polls before a wait gives up
+
+    def __init__(self, reducer):
         nb = len(reducer.buckets)
-        self.reducer, self.arena = reducer, arena
-        self.sync = torch.zeros(FlaggedStep.FLAG0 + 2 * nb + 16, dtype=torch.int32, device=device)
-        self.starts = torch.tensor([lo for lo, _ in reducer.buckets], dtype=torch.int64, device=device)
+        dev = reducer.arena.device
+        self.reducer = reducer
+        self.sync = torch.zeros(self.FLAG0 + 2 * nb + 16, dtype=torch.int32, device=dev)
+        self.starts = torch.tensor([lo for lo, _ in reducer.buckets], dtype=torch.int64, device=dev)
         K.check(K._lib.load().icka_dp_init(), "icka_dp_init")
-        self.polls = int(os.environ.get("ICKA_DP_WAIT_POLLS", FlaggedStep.WAIT_POLLS))
-        self.flag_ptr = [self.sync.data_ptr() + 4 * (FlaggedStep.FLAG0 + i) for i in range(nb)]
-        self.bad_ptr = [self.sync.data_ptr() + 4 * (FlaggedStep.FLAG0 + nb + i) for i in range(nb)]
+        self.polls = int(os.environ.get("ICKA_DP_WAIT_POLLS", self.WAIT_POLLS))
+        base = self.sync.data_ptr()
+        self.flag_ptr = [base + 4 * (self.FLAG0 + i) for i in range(nb)]
+        self.bad_ptr = [base + 4 * (self.FLAG0 + nb + i) for i in range(nb)]
+        self.never_ptr = base + 4 * (self.FLAG0 + 2 * nb + 8)
+        self.test_late = ()      # tests: buckets whose wait is made to give up (it polls the word no node ever sets)
         self.tag = 0
 
-    def first_node(self) -> None:
-        K.check(K._lib.load().icka_dp_step_bump(self.sync.data_ptr(), K._stream()), "icka_dp_step_bump")
-
-    def before_replay(self) -> None:
-        self.tag += 1                           # == the step counter the capture's first node is about to write
-
-    def after_replay(self, order) -> None:
+    def capture(self, graph, body, who: str):
+        """Capture ``body()`` inside ``graph`` (the caller's ``torch.cuda.graph`` context) on THIS thread -- the flag nodes are
+        launched from inside backward (GradReducer.mark_final) -- with the reducer attached and turning every bucket that
+        becomes ready into a flag-set node; the graph's first node bumps the step word.  Returns (what ``body`` returned, the
+        order the flags rise in, the ``dp.CapturedRows`` of the captured embedding backward)."""
         r = self.reducer
+        cap = _FlagCapture(self.sync)
+        r.arena.reducer = r
+        with r.capturing(cap) as taken, torch.autograd.set_multithreading_enabled(False), graph:
+            K.check(K._lib.load().icka_dp_step_bump(self.sync.data_ptr(), K._stream()), "icka_dp_step_bump")
+            out = body()
+        torch.cuda.synchronize()
+        if sorted(cap.order) != list(range(len(r.buckets))):
+            raise RuntimeError("%s: buckets flagged during capture %s != all %d buckets" % (who, cap.order, len(r.buckets)))
+        return out, cap.order, taken
+
+    def after_replay(self, order, rows=None) -> None:
+        """Behind a replay: per bucket, in flag ``order``, a flag wait and the bucket's eager all-reduce on the communication
+        stream; the row-sparse word-table exchange (``rows``: the capture's ``CapturedRows.args``); the bad words made known
+        to all ranks; the join; the final poison pass."""
+        r = self.reducer
+        self.tag += 1                           # == the step counter the replay's first node wrote
         for idx in order:
-            r.launch_now(idx, wait=(self.flag_ptr[idx], self.tag, self.polls, self.bad_ptr[idx]))
+            late = idx in self.test_late
+            r.launch_now(idx, wait=(self.never_ptr if late else self.flag_ptr[idx], self.tag,
+                                    64 if late else self.polls, self.bad_ptr[idx]))
+        if getattr(r, "sparse_word", None) is not None:
+            # the row-sparse word-table exchange: on the communication stream BEHIND the last bucket's flag wait (the
+            # embedding backward, which leaves the rows, is what makes that bucket final)
+            if rows is not None:
+                r.set_sparse_rows(*rows)
+            r.exchange_sparse(word_written=True, after_current=False)
         nb = len(r.buckets)
-        r.share_bad_words(self.sync[FlaggedStep.FLAG0 + nb:FlaggedStep.FLAG0 + 2 * nb])
+        r.share_bad_words(self.sync[self.FLAG0 + nb:self.FLAG0 + 2 * nb])
         r.join()
-        K.check(K._lib.load().icka_dp_poison_final(self.bad_ptr[0], len(r.buckets), self.tag & 0xFFFFFFFF, self.arena.gflat.data_ptr(),
+        # after the join nothing of this step writes gradients any more: a bucket whose wait gave up gets its NaN here
+        # for good (one launch; the bad words carry the step number, so nothing is ever reset)
+        K.check(K._lib.load().icka_dp_poison_final(self.bad_ptr[0], nb, self.tag & 0xFFFFFFFF, r.arena.gflat.data_ptr(),
                                                   self.starts.data_ptr(), 8, K._stream()), "icka_dp_poison_final")
 
 
@@ -1137,7 +1159,8 @@ class FlaggedStep(_StepBase):
     (icka_dp_flag_wait: bounded spin with s_sleep; a wait that gives up raises a host-visible error word and the bucket's
     cast / cast-back launches then fill it with NaN, dp.GradReducer._allreduce) followed by the bucket's eager all-reduce --
     the tagged-word hand-off of csrc/lstm.hip between two streams.  No collective is captured, no graph has a second branch,
-    the compute stream never waits for the communication stream before the end of the step.
+    the compute stream never waits for the communication stream before the end of the step.  (``_FlagExchange`` holds the
+    flag words and this protocol; ``GraphedModule(reducer=)`` shares it.)
     ``step_fn`` runs forward + backward + ``reducer.finish()`` and returns the loss; ``reducer`` is attached to the arena.
 
     ``inputs`` / per-call refresh as ``GraphedStep``.  ``accumulate=k`` (the reference's gradient_accumulation_steps,
@@ -1146,8 +1169,21 @@ class FlaggedStep(_StepBase):
     gradient stores accumulate (k > 1) and whose buckets carry the sum of the k micro-batches.  A cycle also restarts
     whenever the caller dropped the gradients (``zero_grad``) before its k-th call."""
 
-    FLAG0 = 16           # sync words: [0] step counter (bumped by the graph's first node), [FLAG0 + i] flag of bucket i
-    WAIT_POLLS = 1 << 20   # ~3 s of s_sleep(64) polls before a wait gives up
+    _name = "FlaggedStep"
+    FLAG0 = _FlagExchange.FLAG0
+
+    # the exchange's sync words and its late-wait test hook, where the step's callers and tests reach for them
+    @property
+    def sync(self) -> torch.Tensor:
+        return self._xch.sync
+
+    @property
+    def _test_late(self):
+        return self._xch.test_late
+
+    @_test_late.setter
+    def _test_late(self, buckets) -> None:
+        self._xch.test_late = buckets
 
     def __init__(self, model: torch.nn.Module, step_fn: Callable[..., torch.Tensor], reducer, warmup: int = 3, inputs=None,
                  accumulate: int = 1):
@@ -1161,28 +1197,16 @@ class FlaggedStep(_StepBase):
         self._setup(model, step_fn, inputs)
         self.reducer = reducer
         self.accumulate = int(accumulate)
+        self._cycle = _Cycle(self.accumulate)
         self._graphs = None
         self.graph = None
-        dev = self.device
-        nb = len(reducer.buckets)
-        # sync words: [0] step counter, [FLAG0 + i] flag of bucket i, [FLAG0 + nb + i] BAD word of bucket i (the step number
-        # of a wait that gave up)
-        self.sync = torch.zeros(self.FLAG0 + 2 * nb + 16, dtype=torch.int32, device=dev)
-        self._starts = torch.tensor([lo for lo, _ in reducer.buckets], dtype=torch.int64, device=dev)
-        K.check(K._lib.load().icka_dp_init(), "icka_dp_init")
+        self._xch = _FlagExchange(reducer)
         self._warm(max(warmup, 2))              # collective phase, the same on every rank (the first step calibrates the reducer)
         self.arena = model._icka_arena
-        self._polls = int(os.environ.get("ICKA_DP_WAIT_POLLS", self.WAIT_POLLS))
-        self._flag_ptr = [self.sync.data_ptr() + 4 * (self.FLAG0 + i) for i in range(nb)]
-        self._bad_ptr = [self.sync.data_ptr() + 4 * (self.FLAG0 + nb + i) for i in range(nb)]
-        self._test_late = ()     # tests: buckets whose wait is made to give up (it polls a word that no node ever sets)
-        self._never_ptr = self.sync.data_ptr() + 4 * (self.FLAG0 + 2 * nb + 8)
-        self._tag = 0
-        self._micro = 0
         self._graphs = {}        # (accumulate, exchange) -> CUDAGraph
         self._loss = {}
         self._order = {}         # exchange graphs: the order their flags rise in
-        self._sparse_args = {}
+        self._rows = {}          # exchange graphs: the row / id buffers their embedding backward registered (CapturedRows.args)
         model.zero_grad()                       # gradients dropped -> captured kernels overwrite (beta = 0)
         first = (False, self.accumulate == 1)
         self._capture_agreed(*first)            # local capture phase, then the vote: raises on EVERY rank or on none
@@ -1195,120 +1219,57 @@ class FlaggedStep(_StepBase):
     def _capture_agreed(self, accumulate: bool, exchange: bool) -> None:
         """``_capture`` (which issues no process-group traffic: flag nodes only) + the vote over the store: unless the capture
         worked on every rank, every rank raises ``dp.CaptureDisagreement`` -- the ranks fall back together."""
-        from .dp import CaptureDisagreement, all_ranks_agree
         err = None
         try:
             self._capture(accumulate, exchange)
         except Exception as e:  # noqa: BLE001
             err = e
             _end_capture_quietly()
-        if all_ranks_agree(err is None, self.reducer.group, "FlaggedStep capture (accumulate=%s, exchange=%s)" % (accumulate, exchange)):
+        if _agreed(self.reducer, err, "FlaggedStep capture (accumulate=%s, exchange=%s)" % (accumulate, exchange)):
             return
         key = (accumulate, exchange)
         self._graphs.pop(key, None)
         self._loss.pop(key, None)
-        self.reducer.abort_step()
-        self.arena.reducer = self.reducer
         if not self._graphs:                    # the first capture: this object never came to life
             self.model.zero_grad()
             self.close()
-        if err is None:
-            raise CaptureDisagreement("FlaggedStep: another rank could not capture the step")
-        raise CaptureDisagreement("FlaggedStep: this rank could not capture the step (%s: %s)" % (type(err).__name__, err)) from err
+        raise _disagreement("FlaggedStep", "the step", err) from err
 
     def _capture(self, accumulate: bool, exchange: bool) -> None:
-        reducer, arena = self.reducer, self.arena
         if accumulate:
-            arena.attach_grads(self._grad_slots)
+            self.arena.attach_grads(self._grad_slots)
         g = torch.cuda.CUDAGraph()
         key = (accumulate, exchange)
+        graph = torch.cuda.graph(g, stream=self.side, capture_error_mode="thread_local")
         if exchange:
-            cap = _FlagCapture(self.sync)
-            reducer.capture = cap
-            arena.reducer = reducer
-            try:
-                # backward on THIS thread: the flag nodes are launched from inside backward (GradReducer.mark_final)
-                with torch.autograd.set_multithreading_enabled(False), \
-                        torch.cuda.graph(g, stream=self.side, capture_error_mode="thread_local"):
-                    K.check(K._lib.load().icka_dp_step_bump(self.sync.data_ptr(), K._stream()), "icka_dp_step_bump")
-                    K.bump_dropout_nonce(self.nonce)
-                    self._loss[key] = self._step()   # its reducer.finish() reports the remaining buckets (flags at the end)
-                    _test_fail("flagged")
-            finally:
-                reducer.capture = None
-            torch.cuda.synchronize()
-            if sorted(cap.order) != list(range(len(reducer.buckets))):
-                raise RuntimeError("FlaggedStep: buckets flagged during capture %s != all %d buckets"
-                                   % (cap.order, len(reducer.buckets)))
-            self._order[key] = cap.order
-            # (the captured embedding backward registered its static row / id buffers: the same ones every replay fills; a step
-            # whose embedding backward wrote the table densely -- the fp32-exact mode -- leaves None: dense mean of the slot)
-            if getattr(reducer, "sparse_word", None) is not None:
-                self._sparse_args[key] = reducer._sparse
-                reducer._sparse, reducer._word_written = None, False
+            def step():
+                K.bump_dropout_nonce(self.nonce)
+                loss = self._step()             # its reducer.finish() reports the remaining buckets (flags at the end)
+                _test_fail("flagged")
+                return loss
+            self._loss[key], self._order[key], taken = self._xch.capture(graph, step, "FlaggedStep")
+            self._rows[key] = taken.args
         else:
             # a micro-batch that is not the last of its cycle: the same step with the reducer detached (no wire copies, no
-            # flags) and muted (the step_fn's reducer.finish() returns at once for the duration of the capture)
-            arena.reducer = None
-            reducer.muted = True                # finish() returns at once: nothing is exchanged, no bucket state moves
-            try:
-                with torch.autograd.set_multithreading_enabled(False), \
-                        torch.cuda.graph(g, stream=self.side, capture_error_mode="thread_local"):
-                    K.bump_dropout_nonce(self.nonce)
-                    self._loss[key] = self._step()
-            finally:
-                arena.reducer = reducer
-                reducer.muted = False
+            # flags) and muted (the step_fn's reducer.finish() returns at once: nothing is exchanged, no bucket state moves)
+            with self.reducer.muted_detached(), torch.autograd.set_multithreading_enabled(False), graph:
+                K.bump_dropout_nonce(self.nonce)
+                self._loss[key] = self._step()
             torch.cuda.synchronize()
         self._graphs[key] = g
 
     def __call__(self, *args, **kwargs) -> torch.Tensor:
-        if self._graphs is None:
-            raise RuntimeError("FlaggedStep is closed")
-        self._refresh(args, kwargs)
-        if self.arena.shadow_policy != "always":
-            self.arena.sync()
-        K.lstm_check_error("detected before a FlaggedStep replay")
-        K.gemm_ln_check_error("detected before a FlaggedStep replay")
-        K.dp_check_error("detected before a FlaggedStep replay")
+        self._prepare(self._graphs is None, self._values(args, kwargs), flags=True)
         accumulate, stale = self._cycle_state()
-        if not accumulate:
-            self._micro = 0                     # the caller dropped the gradients: a new cycle starts here
-        exchange = self._micro == self.accumulate - 1
+        exchange = self._cycle.exchanges(accumulate)
         key = (accumulate, exchange)
         if key not in self._graphs:
             self._capture_agreed(*key)
         self._zero(stale)
-        if exchange:
-            self._tag += 1                      # == the step counter the graph's first node is about to write
         self._graphs[key].replay()
         if exchange:
-            r = self.reducer
-            for idx in self._order[key]:
-                late = idx in self._test_late
-                r.launch_now(idx, wait=(self._never_ptr if late else self._flag_ptr[idx], self._tag,
-                                        64 if late else self._polls, self._bad_ptr[idx]))
-            if getattr(r, "sparse_word", None) is not None:
-                # the row-sparse word-table exchange: on the communication stream BEHIND the last bucket's flag wait (the
-                # embedding backward, which leaves the rows, is what makes that bucket final)
-                if self._sparse_args[key] is not None:
-                    r.set_sparse_rows(*self._sparse_args[key])
-                with torch.cuda.stream(r.comm_stream):
-                    r._exchange_on_current = True
-                    try:
-                        r.exchange_sparse(word_written=True)
-                    finally:
-                        r._exchange_on_current = False
-            nb = len(r.buckets)
-            r.share_bad_words(self.sync[self.FLAG0 + nb:self.FLAG0 + 2 * nb])
-            r.join()
-            # after the join nothing of this step writes gradients any more: a bucket whose wait gave up gets its NaN here
-            # for good (one launch; the bad words carry the step number, so nothing is ever reset)
-            K.check(K._lib.load().icka_dp_poison_final(self._bad_ptr[0], nb, self._tag & 0xFFFFFFFF, self.arena.gflat.data_ptr(),
-                                                      self._starts.data_ptr(), 8, K._stream()), "icka_dp_poison_final")
-            self._micro = 0
-        else:
-            self._micro += 1
+            self._xch.after_replay(self._order[key], self._rows[key])
+        self._cycle.done(exchange)
         self.arena.attach_grads(self._grad_slots)
         self.loss = self._loss[key]
         return self.loss
@@ -1356,7 +1317,6 @@ def build_step(model: torch.nn.Module, step_fn: Callable[..., torch.Tensor], inp
     say = log or (lambda msg: None)
     if not graph:
         return step_fn, "eager"
-    arena = model._icka_arena
     if reducer is None:
         try:
             say("capturing the step into a hipGraph")
@@ -1365,7 +1325,7 @@ def build_step(model: torch.nn.Module, step_fn: Callable[..., torch.Tensor], inp
             say("graph capture failed (%s: %s); running eagerly" % (type(e).__name__, e))
             _end_capture_quietly()
             return step_fn, "eager"
-    from .dp import CaptureDisagreement, all_ranks_agree
+    from .dp import CaptureDisagreement
     nccl = reducer.is_cuda and reducer.backend == "nccl"
     if capture_collectives:
         # the all-reduces INSIDE one hipGraph (side-stream branches): needs a capturable collective library
@@ -1376,11 +1336,9 @@ def build_step(model: torch.nn.Module, step_fn: Callable[..., torch.Tensor], inp
         except Exception as e:  # noqa: BLE001
             err = e
             _end_capture_quietly()
-        if all_ranks_agree(err is None, reducer.group, "captured-collectives step"):
+        if _agreed(reducer, err, "captured-collectives step"):
             return st, "hipgraph(collectives captured, %d buckets)" % len(reducer.buckets)
         say("capture with collectives failed on %s" % ("this rank (%s: %s)" % (type(err).__name__, err) if err else "another rank"))
-        reducer.abort_step()
-        arena.reducer = reducer
     else:
         forms = (["flagged"] if (prefer == "flagged" and nccl) else []) + ["segmented"]
         for form in forms:
@@ -1396,22 +1354,17 @@ def build_step(model: torch.nn.Module, step_fn: Callable[..., torch.Tensor], inp
                 say("%s capture not taken: %s" % (form, e))
     # last graph form: forward + backward only, captured with the reducer detached and muted (step_fn's finish() returns at once)
     err, cap = None, None
-    arena.reducer = None
-    reducer.muted = True
     try:
         say("capturing forward + backward only (the gradient all-reduce runs eagerly after each replay)")
-        cap = _StepCapture(model, step_fn, inputs=inputs)
+        with reducer.muted_detached():
+            cap = _StepCapture(model, step_fn, inputs=inputs)
     except Exception as e:  # noqa: BLE001
         err = e
         _end_capture_quietly()
-    finally:
-        arena.reducer = reducer
-        reducer.muted = False
-    if all_ranks_agree(err is None, reducer.group, "compute-only capture"):
+    if _agreed(reducer, err, "compute-only capture"):
         return _ComputeThenReduce(cap, reducer), "hipgraph(compute)+eager-allreduce"
     say("compute-only capture failed on %s; running eagerly"
         % ("this rank (%s: %s)" % (type(err).__name__, err) if err else "another rank"))
     if cap is not None:
         cap.close()
-    reducer.abort_step()
     return step_fn, "eager"
