@@ -148,6 +148,12 @@ PROTOTYPES = {
                              c_vp]),
     "icka_add_bf16": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp]),
     "icka_tanh_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "icka_contrastive_workspace_floats": (c_i64, [c_i32]),
+    "icka_contrastive_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "icka_contrastive_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_i32, c_vp, c_vp]),
+    "icka_relu_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "icka_sample_swap": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "icka_dgelu_bf16": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp]),
     "icka_embed_prompt_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
                                       c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_u64, c_vp]),

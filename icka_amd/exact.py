@@ -848,3 +848,34 @@ def prompt_mapping(A: ParamArena, x, lin1, lin2, p: float):
     if p > 0:
         h = DropoutFn.apply(h, A, p)
     return LinearFn.apply(A.anchor, h, lin2, A, False)
+
+
+class ReluHeadFn(torch.autograd.Function):
+    """fp32 form of ops.ReluHeadFn: Linear(in, N1) -> ReLU -> Linear(N1, N2) on [rows, in] f32 (the contrastive projection
+    heads, gate_cl_modeling.py:1387-1388).  The ReLU runs on the ReLU-backward kernel (relu(x) = x * [x > 0])."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, lin1, lin2, A: ParamArena):
+        from . import kernels as K
+        M = x.shape[0]
+        h = gemm(GEMM_NT, x, _fw(A, lin1.weight), _new(x, M, lin1.weight.shape[0]), bias=lin1.bias)
+        K.relu_bwd(h, h, h)
+        y = gemm(GEMM_NT, h, _fw(A, lin2.weight), _new(x, M, lin2.weight.shape[0]), bias=lin2.bias)
+        ctx.lin1, ctx.lin2, ctx.A = lin1, lin2, A
+        ctx.need_dx = x.requires_grad
+        ctx.save_for_backward(x, h)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import kernels as K
+        x, h = ctx.saved_tensors
+        lin1, lin2, A = ctx.lin1, ctx.lin2, ctx.A
+        dy = _cf(dy)
+        _linear_bwd_params(A, dy, h, lin2.weight, lin2.bias)
+        dh = gemm(GEMM_NN, dy, _fw(A, lin2.weight), torch.empty(h.shape, dtype=F32, device=h.device))
+        K.relu_bwd(dh, h, dh)
+        _linear_bwd_params(A, dh, x, lin1.weight, lin1.bias)
+        dx = gemm(GEMM_NN, dh, _fw(A, lin1.weight), torch.empty(x.shape, dtype=F32, device=x.device)) if ctx.need_dx else None
+        A.flush_final()
+        return None, dx, None, None, None

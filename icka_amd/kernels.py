@@ -1099,3 +1099,78 @@ def crs_bwd(dcrs, seq, cross, W, dseq, dcross, dW, dbias, B, S, accumulate):
     check(_lib.load().icka_crs_bwd(dcrs.data_ptr(), seq.data_ptr(), seq.stride(0), cross.data_ptr(), cross.stride(0),
                                    W.data_ptr(), dseq.data_ptr(), dcross.data_ptr(), dW.data_ptr(), _ptr(dbias), B, S, H,
                                    int(accumulate), _stream()), "icka_crs_bwd")
+
+
+# ------------------------------------------------------------------------------------------------- auxiliary objective
+_OBJ_DTYPE = {F32: 0, BF16: 1, F16: 2}
+
+
+def _obj_rows(t, v):
+    for n, x in (("t", t), ("v", v)):
+        _dev(x, n)
+        if x.dtype not in _OBJ_DTYPE or x.dim() != 2 or x.stride(1) != 1:
+            raise ValueError("%s must be 2-D row-major f32 / bf16 / fp16" % n)
+    if t.dtype != v.dtype or t.shape != v.shape:
+        raise ValueError("t and v must have one dtype and shape, got %s %s / %s %s" % (t.dtype, tuple(t.shape), v.dtype,
+                                                                                       tuple(v.shape)))
+    B, D = t.shape
+    if not (1 <= B <= 256) or D % 8 or not (8 <= D <= 4096):
+        raise ValueError("contrastive loss: 1 <= B <= 256 and D a multiple of 8 in [8, 4096], got B=%d D=%d" % (B, D))
+    return B, D
+
+
+def contrastive_workspace(B: int, device) -> torch.Tensor:
+    return torch.empty(int(_lib.load().icka_contrastive_workspace_floats(B)), dtype=F32, device=device)
+
+
+def contrastive_fwd(t, v, temp: float, temp_lamb: float, stats, ws, crs=None, n_neg: int = 0):
+    """stats f32[2] = (contrastive loss, relevance cross-entropy or 0); ws keeps what the backward reads."""
+    B, D = _obj_rows(t, v)
+    if crs is not None and (crs.dtype != F32 or tuple(crs.shape) != (B, 2) or not crs.is_contiguous()):
+        raise ValueError("crs must be contiguous f32 [B, 2]")
+    check(_lib.load().icka_contrastive_fwd(t.data_ptr(), t.stride(0), v.data_ptr(), v.stride(0), _OBJ_DTYPE[t.dtype], B, D,
+                                           float(temp), float(temp_lamb), _ptr(crs), int(n_neg), stats.data_ptr(),
+                                           ws.data_ptr(), _stream()), "icka_contrastive_fwd")
+    return stats
+
+
+def contrastive_bwd(t, v, temp: float, temp_lamb: float, ws, dcl, dt, dv, crs=None, n_neg: int = 0, dcrs=None, dcrs_loss=None):
+    """dt, dv (contiguous f32, any input dtype) from the device-resident upstream gradient dcl (f32, one element) of the contrastive
+    loss; with crs also dcrs f32 [B,2] from dcrs_loss, the upstream gradient of the relevance cross-entropy."""
+    B, D = _obj_rows(t, v)
+    for n, x in (("dt", dt), ("dv", dv)):
+        if x.dtype != F32 or tuple(x.shape) != (B, D) or not x.is_contiguous():
+            raise ValueError("%s must be contiguous f32 [%d, %d]" % (n, B, D))
+    for n, x in (("dcl", dcl), ("dcrs_loss", dcrs_loss)):
+        if x is not None and (x.dtype != F32 or x.numel() != 1):
+            raise ValueError("%s must be one f32 element" % n)
+    if crs is not None and (dcrs is None or dcrs_loss is None or dcrs.dtype != F32 or tuple(dcrs.shape) != (B, 2)
+                            or not dcrs.is_contiguous()):
+        raise ValueError("with crs: dcrs contiguous f32 [B, 2] and dcrs_loss")
+    check(_lib.load().icka_contrastive_bwd(t.data_ptr(), t.stride(0), v.data_ptr(), v.stride(0), _OBJ_DTYPE[t.dtype], B, D,
+                                           float(temp), float(temp_lamb), ws.data_ptr(), dcl.data_ptr(), _ptr(dcrs_loss), dt.data_ptr(),
+                                           dv.data_ptr(), _ptr(crs), int(n_neg), _ptr(dcrs), _stream()),
+          "icka_contrastive_bwd")
+
+
+def relu_bwd(dy, y, dx):
+    """dx = dy * [y > 0], contiguous bf16 or f32 (relu_bwd(x, x, out) = relu(x))."""
+    for n, t in (("dy", dy), ("y", y), ("dx", dx)):
+        _dev(t, n)
+        if t.dtype not in (BF16, F32) or t.dtype != y.dtype or not t.is_contiguous():
+            raise ValueError("%s must be contiguous bf16 or f32 (one dtype)" % n)
+    if dy.numel() != y.numel() or dx.numel() != y.numel():
+        raise ValueError("relu_bwd: size mismatch")
+    check(_lib.load().icka_relu_bwd(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), y.numel(), int(y.dtype == F32), _stream()),
+          "icka_relu_bwd")
+    return dx
+
+
+def sample_swap(x, y, B: int, n_neg: int):
+    """y = x with the negative-sample pairs of the last n_neg of B samples exchanged (x, y contiguous, same shape)."""
+    _dev(x, "x"); _dev(y, "y")
+    if not (x.is_contiguous() and y.is_contiguous()) or x.dtype != y.dtype or x.shape != y.shape or x.numel() % B:
+        raise ValueError("sample_swap: x and y contiguous, one dtype and shape, B samples")
+    check(_lib.load().icka_sample_swap(x.data_ptr(), y.data_ptr(), B, x.numel() // B * x.element_size(), int(n_neg), _stream()),
+          "icka_sample_swap")
+    return y

@@ -629,25 +629,38 @@ class BertModel(BertPreTrainedModel):
         return encoded_layers, pooled_output
 
 
-def _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att):
+def _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att, pool=False):
     """Shared trunk of the MNER heads: BERT text encoder -> dropout -> region tokens -> vismap2text -> text->image cross
     encoder (cl_modeling.py:1341-1361 = Cross_Modal_Interaction_Module.py:949-969 / :2446-2466).  ``self`` provides
     ``config, bert, vismap2text, txt2img_attention``.  Returns (arena, seq bf16 [B*S,H], its f32 twin or None,
-    cross bf16 [B*S,H], its f32 twin)."""
+    cross bf16 [B*S,H], its f32 twin), followed by the pooled output [B,H] of the last encoder layer, taken before the
+    dropout (gate_cl_modeling.py:1322-1326), when ``pool``."""
     cfg = self.config
     B, S = input_ids.shape
     H = cfg.hidden_size
     A = self._arena()
     dev = input_ids.device
     # ---- text encoder (cl_modeling.py:1341-1344)
+    pooled = None
     if isinstance(self.bert, BertModel):
         sequence_output = self.bert.encode(input_ids, segment_ids, input_mask, output_all_encoded_layers=False)[-1]
+        if pool:
+            # the last layer feeds the pooler and the head: one fan-out node sums the two gradients (as for seq below)
+            seqf = _twin(sequence_output)
+            if not _is_exact(self) and torch.is_grad_enabled() and sequence_output.requires_grad:
+                to_pool, so = ops.FanOutFn.apply(sequence_output.view(B * S, H), 2)
+                sequence_output = _with_twin(so, seqf, (B, S, H))
+                pooled = self.bert.pooler(to_pool.view(B, S, H))
+            else:
+                pooled = self.bert.pooler(sequence_output)
     else:   # a caller-supplied text encoder with the reference's BertModel call convention
-        sequence_output, _ = self.bert(input_ids, token_type_ids=segment_ids, attention_mask=input_mask,
-                                       output_all_encoded_layers=False)
+        sequence_output, pooled = self.bert(input_ids, token_type_ids=segment_ids, attention_mask=input_mask,
+                                            output_all_encoded_layers=False)
+    tail = (pooled,) if pool else ()
     exact = _is_exact(self)
     if exact:
-        return _mner_trunk_exact(self, A, sequence_output.view(B * S, H), added_attention_mask, visual_embeds_att, B, S)
+        return _mner_trunk_exact(self, A, sequence_output.view(B * S, H), added_attention_mask, visual_embeds_att, B,
+                                 S) + tail
     seq = sequence_output.view(B * S, H)
     seqf = _twin(sequence_output)
     if self.training and cfg.hidden_dropout_prob > 0:
@@ -690,7 +703,7 @@ def _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, 
         d = _dims(cfg, B, S, R, self.training, mixed=_is_mixed(layer))
         cross, crossf = ops.CrossLayerFn.apply(A.anchor, cross, crossf, vis, layer, A, img_mask, d,
                                                vis16 if d.h16 else None)
-    return A, seq, seqf, cross, crossf
+    return (A, seq, seqf, cross, crossf) + tail
 
 
 def _region_layout(v: torch.Tensor):
@@ -725,18 +738,25 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
 
     forward(input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_mean, visual_embeds_att,
             temp=None, temp_lamb=None, lamb=None, labels=None, negative_rate=None)
-    keeps the reference's positional signature (gate_cl_modeling.py:1319-1320).  The hot path ends at the per-token
-    logits (``bert_feats``): with ``labels=None`` the logits ``[B,S,num_labels]`` (f32) are returned; with labels,
-    the token-level cross-entropy over valid tokens (the benchmark loss).  The CRF and the
-    contrastive / crs auxiliary losses of the reference are outside the hot path; a caller that owns a CRF module
-    can assign it to ``self.crf`` and gets ``-crf(logits, labels, mask, reduction='mean')`` like the reference.
+    keeps the reference's positional signature (gate_cl_modeling.py:1319-1320).  With ``labels=None`` the logits
+    ``[B,S,num_labels]`` (f32) are returned (the CRF's decode when ``self.crf`` is set).  With labels, the main loss:
+    ``-crf(logits, labels, mask, reduction='mean')`` when ``self.crf`` is set (``use_crf=True`` or assigned by the
+    caller), else the token-level cross-entropy over valid tokens (the benchmark loss).
+
+    ``aux_losses=True`` builds the reference's contrastive projection heads (``text_dense_cl``, ``text_ouput_cl`` -- the
+    reference's spelling --, ``image_dense_cl``, ``image_output_cl``) and, with labels, returns the reference's full
+    training objective (csrc/objective.hip): ``lamb * main + (1 - lamb) * (crs_loss + cl_loss)`` for gate_cl
+    (gate_cl_modeling.py:1385-1395; the last ``negative_rate`` samples get their cross-modal stream swapped pairwise and
+    relevance label 0), ``0.88 * main + 0.12 * cl_loss`` for cl (cl_modeling.py:1376-1382).  ``temp`` and ``temp_lamb``
+    (and ``lamb`` for gate_cl) are then required.  ``aux_losses=False`` (the default) has neither the heads nor the
+    auxiliary terms, and ``labels=None`` returns the same logits either way.
 
     ``visual_embeds_att`` is the myResnet 'att' tensor ``[B,2048,7,7]`` (R = 49, reference layout) or region
     tokens ``[B,R,2048]`` (BASELINE synthetic layout); ``regions`` defaults to 49 as in the reference.
     """
 
     def __init__(self, config, layer_num1=1, layer_num2=1, layer_num3=1, num_labels=2, regions=49, variant="cl",
-                 max_seq_length=128, cross_attention_fp8=False, use_crf=False):
+                 max_seq_length=128, cross_attention_fp8=False, use_crf=False, aux_losses=False):
         super().__init__(config)
         check_config(config)
         if variant not in ("cl", "gate_cl"):
@@ -758,6 +778,12 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
         self.Gate_text = nn.Linear(config.hidden_size, config.hidden_size)
         self.Gate_image = nn.Linear(config.hidden_size, config.hidden_size)
         self.classifier = nn.Linear(config.hidden_size * 2, num_labels)
+        self.aux_losses = bool(aux_losses)
+        if self.aux_losses:   # contrastive projection heads (gate_cl_modeling.py:1272-1276; reference names and shapes)
+            self.text_dense_cl = nn.Linear(config.hidden_size, config.hidden_size)
+            self.text_ouput_cl = nn.Linear(config.hidden_size, config.hidden_size)
+            self.image_dense_cl = nn.Linear(2048, config.hidden_size)
+            self.image_output_cl = nn.Linear(config.hidden_size, config.hidden_size)
         # the reference builds torchcrf.CRF(num_labels, batch_first=True) here (cl_modeling.py:1269); use_crf=True builds
         # the HIP-backed equivalent (icka_amd.crf.CRF), any object with the same call/decode API may be assigned later
         self.crf = None
@@ -767,11 +793,24 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
         self.apply(self.init_bert_weights)
 
     def logits(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att):
+        return self._feats(input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att)[0]
+
+    def _feats(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att, n_swap=0, pool=False):
+        """(logits, relevance logits crs [B,2] or None, pooled [B,H] or None).  ``n_swap`` >= 2 (gate_cl, training objective):
+        the negative-sample swap of the last n_swap samples' cross-modal stream, which then feeds both the relevance
+        classifier and the gate (gate_cl_modeling.py:1345-1382)."""
         cfg = self.config
         B, S = input_ids.shape
         H = cfg.hidden_size
-        A, seq, seqf, cross, crossf = _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask,
-                                                  visual_embeds_att)
+        trunk = _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att, pool=pool)
+        A, seq, seqf, cross, crossf = trunk[:5]
+        pooled = trunk[5] if pool else None
+        crs = None
+        if self.variant == "gate_cl" and n_swap >= 2:
+            if crossf is not None and _is_mixed(self):     # the fp16 twin feeds the mixed16 gate: swapped alongside
+                cross, crossf = ops.SampleSwapFn.apply(cross, B, n_swap, crossf)
+            else:                                          # the bf16 mode's f32 twin has no consumer past this point
+                cross, crossf = ops.SampleSwapFn.apply(cross, B, n_swap), None
         if self.variant == "gate_cl":
             # P = softmax(crs_classifier(cat(seq, cross).view(B,-1)))[:, -1];  cross = P * cross   (:1364-1373)
             if self.crs_classifier.weight.shape[1] != 2 * H * S:
@@ -797,7 +836,7 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
                     cross = ops.SampleGateFn.apply(cross, None, crs, 1, B, S)
         # ---- gate + classifier (:1363-1371)
         if _is_exact(self):
-            return X.GatedHeadFn.apply(A.anchor, seq, cross, self, A).view(B, S, self.num_labels)
+            return X.GatedHeadFn.apply(A.anchor, seq, cross, self, A).view(B, S, self.num_labels), crs, pooled
         seq16 = cross16 = None
         if _is_mixed(self):
             # the fp16 twins of the two streams (left by the last encoder / cross layer / relevance gate; made from the bf16
@@ -806,7 +845,7 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
             seq16 = ops._fwd_twin(A, seq, seqf, d16)
             cross16 = ops._fwd_twin(A, cross, crossf, d16)
         logits = ops.GatedHeadFn.apply(A.anchor, seq, cross, self, A, seq16, cross16)
-        return logits.view(B, S, self.num_labels)
+        return logits.view(B, S, self.num_labels), crs, pooled
 
     def forward(self, input_ids, segment_ids=None, input_mask=None, added_attention_mask=None, visual_embeds_mean=None,
                 visual_embeds_att=None, temp=None, temp_lamb=None, lamb=None, labels=None, negative_rate=None, *,
@@ -838,6 +877,9 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
             R = visual_embeds_att.shape[1] if visual_embeds_att.dim() == 3 else visual_embeds_att.shape[2] * visual_embeds_att.shape[3]
             added_attention_mask = torch.cat([torch.ones(input_ids.shape[0], R, dtype=input_mask.dtype, device=input_mask.device),
                                               input_mask], dim=1)
+        if labels is not None and self.aux_losses:
+            return self._objective(input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_mean,
+                                   visual_embeds_att, temp, temp_lamb, lamb, labels, negative_rate)
         logits = self.logits(input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att)
         if labels is None:
             if self.crf is not None:   # cl_modeling.py:1386: pred_tags = self.crf.decode(feats, mask=input_mask.byte())
@@ -846,6 +888,49 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
         if self.crf is not None:
             return -self.crf(logits, labels, mask=input_mask.byte(), reduction="mean")
         return token_ce_loss(logits, labels, input_mask, exact=_is_exact(self))
+
+    def _main_loss(self, logits, labels, input_mask):
+        if self.crf is not None:
+            return -self.crf(logits, labels, mask=input_mask.byte(), reduction="mean")
+        return token_ce_loss(logits, labels, input_mask, exact=_is_exact(self))
+
+    def _objective(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_mean, visual_embeds_att,
+                   temp, temp_lamb, lamb, labels, negative_rate):
+        """The reference's training loss with labels (gate_cl_modeling.py:1385-1395 / cl_modeling.py:1376-1382)."""
+        gate = self.variant == "gate_cl"
+        for name, val in (("temp", temp), ("temp_lamb", temp_lamb)) + ((("lamb", lamb),) if gate else ()):
+            if val is None:
+                raise ValueError("aux_losses=True: forward() with labels needs %s" % name)
+        if visual_embeds_mean is None:
+            raise ValueError("aux_losses=True: forward() with labels needs visual_embeds_mean")
+        B = input_ids.shape[0]
+        if visual_embeds_mean.shape[0] != B or visual_embeds_mean.shape[-1] != 2048 or not visual_embeds_mean.is_cuda:
+            raise ValueError("visual_embeds_mean must be a [B, 2048] ROCm tensor")
+        H = self.config.hidden_size
+        if not (1 <= B <= 256) or H % 8 or H > 4096:
+            raise ValueError("aux_losses: the contrastive loss takes 1 <= B <= 256 samples and hidden sizes that are multiples "
+                             "of 8 up to 4096, got B=%d H=%d" % (B, H))
+        # negatives: the last negative_rate samples when the batch is larger (gate_cl_modeling.py:1345-1356)
+        n_neg = int(negative_rate) if (gate and negative_rate is not None and B > negative_rate) else 0
+        logits, crs, pooled = self._feats(input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att,
+                                          n_swap=n_neg, pool=True)
+        main = self._main_loss(logits, labels, input_mask)
+        A = arena_of(self)
+        vm = visual_embeds_mean.reshape(B, 2048)
+        if _is_exact(self):
+            vm = vm if vm.dtype == F32 and vm.is_contiguous() else vm.float().contiguous()
+            t = X.ReluHeadFn.apply(A.anchor, pooled, self.text_dense_cl, self.text_ouput_cl, A)
+            v = X.ReluHeadFn.apply(A.anchor, vm, self.image_dense_cl, self.image_output_cl, A)
+        else:
+            if vm.dtype != BF16:
+                vm = K.cast_f32_to_bf16(vm.float().contiguous(), torch.empty(B, 2048, dtype=BF16, device=vm.device))
+            t = ops.ReluHeadFn.apply(A.anchor, pooled, self.text_dense_cl, self.text_ouput_cl, A)
+            v = ops.ReluHeadFn.apply(A.anchor, vm.contiguous(), self.image_dense_cl, self.image_output_cl, A)
+        cl_loss, crs_loss = ops.ContrastiveFn.apply(t, v, crs if gate else None, n_neg, float(temp), float(temp_lamb))
+        if gate:
+            lamb = float(lamb)
+            return lamb * main + (1.0 - lamb) * (crs_loss + cl_loss)
+        return 0.88 * main + 0.12 * cl_loss
 
 
 class MTCCMBertForMMTokenClassificationCRF_gate_1(BertPreTrainedModel):

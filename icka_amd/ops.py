@@ -1030,3 +1030,100 @@ class TokenCEFn(torch.autograd.Function):
                                                       dl.numel(), K._stream())
         K.check(check_rc, "icka_x_scale_by_ratio")
         return out, None, None
+
+
+# =============================================================================================== auxiliary objective
+# The training loss of the gated taggers with aux_losses=True (gate_cl_modeling.py:1276-1395, cl_modeling.py:1376-1382):
+# two ReLU projection heads, the text <-> image contrastive loss, the relevance cross-entropy and the negative-sample swap.
+class ReluHeadFn(torch.autograd.Function):
+    """Linear(in, N1) -> ReLU -> Linear(N1, N2) on [rows, in] bf16 (the contrastive projection heads text_dense_cl /
+    text_ouput_cl and image_dense_cl / image_output_cl, gate_cl_modeling.py:1387-1388).  The output is f32: it feeds only
+    the contrastive loss, whose cosines are taken in f32."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, lin1, lin2, A: ParamArena):
+        M = x.shape[0]
+        h = torch.empty(M, lin1.weight.shape[0], dtype=BF16, device=x.device)
+        K.gemm(K.GEMM_NT, x, A.w(lin1.weight), h, bias=lin1.bias, epilogue=K.EPI_RELU)
+        y = torch.empty(M, lin2.weight.shape[0], dtype=F32, device=x.device)
+        K.gemm(K.GEMM_NT, h, A.w(lin2.weight), y, bias=lin2.bias)
+        ctx.lin1, ctx.lin2, ctx.A = lin1, lin2, A
+        ctx.need_dx = x.requires_grad
+        ctx.save_for_backward(x, h)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, h = ctx.saved_tensors
+        lin1, lin2, A = ctx.lin1, ctx.lin2, ctx.A
+        lib = K._lib.load()
+        M, N2 = dy.shape
+        N1 = h.shape[1]
+        dyb = K.cast_f32_to_bf16(dy if dy.is_contiguous() else dy.contiguous(), torch.empty(M, N2, dtype=BF16, device=dy.device))
+        # second Linear: dW2 = dy^T . h, db2 = colsum(dy), d(h) = dy . W2 -> ReLU backward in place
+        K.gemm(K.GEMM_TN, dyb, h, A.g(lin2.weight), beta=A.grad_beta(lin2.weight))
+        K.colsum(dyb, A.g(lin2.bias), A.workspace("colsum", lib.icka_colsum_workspace_floats(max(N1, N2))),
+                 accumulate=A.grad_beta(lin2.bias) > 0)
+        dh = torch.empty(M, N1, dtype=BF16, device=dy.device)
+        K.gemm(K.GEMM_NN, dyb, A.w(lin2.weight), dh)
+        K.relu_bwd(dh, h, dh)
+        # first Linear
+        K.gemm(K.GEMM_TN, dh, x, A.g(lin1.weight), beta=A.grad_beta(lin1.weight))
+        K.colsum(dh, A.g(lin1.bias), A.workspace("colsum", lib.icka_colsum_workspace_floats(max(N1, N2))),
+                 accumulate=A.grad_beta(lin1.bias) > 0)
+        dx = None
+        if ctx.need_dx:
+            dx = torch.empty_like(x)
+            K.gemm(K.GEMM_NN, dh, A.w(lin1.weight), dx)
+        A.flush_final()
+        return None, dx, None, None, None
+
+
+class ContrastiveFn(torch.autograd.Function):
+    """(cl_loss, crs_loss) of gate_cl_modeling.py:1385-1390 in one launch each way (csrc/objective.hip): the text <-> image
+    InfoNCE loss of the projected rows t, v ([B, D], f32 / bf16) and, with ``crs`` (f32 [B, 2]), the relevance cross-entropy
+    against labels 1 except for the last ``n_neg`` samples (0 otherwise).  The backward reads both upstream gradients from
+    device memory (capture-safe, no host sync)."""
+
+    @staticmethod
+    def forward(ctx, t, v, crs, n_neg: int, temp: float, temp_lamb: float):
+        stats = torch.empty(2, dtype=F32, device=t.device)
+        ws = K.contrastive_workspace(t.shape[0], t.device)
+        K.contrastive_fwd(t, v, temp, temp_lamb, stats, ws, crs=crs, n_neg=n_neg)
+        ctx.n_neg, ctx.temp, ctx.temp_lamb = n_neg, temp, temp_lamb
+        ctx.save_for_backward(t, v, crs, ws)
+        return stats[0:1].view(()), stats[1:2].view(())
+
+    @staticmethod
+    def backward(ctx, dcl, dcrs_loss):
+        t, v, crs, ws = ctx.saved_tensors
+        dt = torch.empty(t.shape, dtype=F32, device=t.device)
+        dv = torch.empty_like(dt)
+        dcrs = torch.empty(crs.shape, dtype=F32, device=crs.device) if crs is not None else None
+        K.contrastive_bwd(t, v, ctx.temp, ctx.temp_lamb, ws, dcl.reshape(1), dt, dv, crs=crs, n_neg=ctx.n_neg, dcrs=dcrs,
+                          dcrs_loss=None if crs is None else dcrs_loss.reshape(1))
+        if t.dtype != F32:     # a 16-bit producer takes its gradient in its own type
+            dt, dv = dt.to(t.dtype), dv.to(v.dtype)
+        return dt, dv, dcrs, None, None, None
+
+
+class SampleSwapFn(torch.autograd.Function):
+    """The negative samples of gate_cl (gate_cl_modeling.py:1345-1356): of the last ``n_neg`` samples of the [B*S, H] stream,
+    sample b0 + i and sample b0 + h + i trade places (b0 = B - n_neg, h = n_neg // 2).  ``x16`` (mixed16): the fp16 twin,
+    swapped alongside and returned as a second, non-differentiable output.  The permutation is its own inverse."""
+
+    @staticmethod
+    def forward(ctx, x, B: int, n_neg: int, x16=None):
+        ctx.B, ctx.n_neg = B, n_neg
+        y = K.sample_swap(x, torch.empty_like(x), B, n_neg)
+        if x16 is None:
+            return y
+        y16 = K.sample_swap(x16, torch.empty_like(x16), B, n_neg)
+        ctx.mark_non_differentiable(y16)
+        ctx.set_materialize_grads(False)
+        return y, y16
+
+    @staticmethod
+    def backward(ctx, dy, _dy16=None):
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        return K.sample_swap(dy, torch.empty_like(dy), ctx.B, ctx.n_neg), None, None, None

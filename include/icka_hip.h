@@ -43,7 +43,9 @@ extern "C" {
  * 6: round 5 -- every tuning setter is GONE (icka_gemm_set_*, icka_ln_set_rows_per_wave, icka_attn_set_whole_head,
  *    icka_lstm_set_persistent / _handoff / _batch_split): icka_gemm_desc grew `tune`; icka_attn_fwd_ex's `fp8` argument became
  *    `flags`; icka_attn_bwd, icka_lstm_fwd and icka_lstm_bwd take `flags`; the 256x256-tile and persistent 12-wave GEMM kernels
- *    those setters switched on left the library (profiles/NEGATIVE_RESULTS.md); icka_gemm_ln, icka_gemm_ln_sync_words, icka_gemm_ln_test_hooks, icka_gemm_qkv_attn (additive). */
+ *    those setters switched on left the library (profiles/NEGATIVE_RESULTS.md); icka_gemm_ln, icka_gemm_ln_sync_words, icka_gemm_ln_test_hooks, icka_gemm_qkv_attn (additive).
+ *    Later, still 6: icka_contrastive_fwd, icka_contrastive_bwd, icka_contrastive_workspace_floats, icka_relu_bwd,
+ *    icka_sample_swap (additive: the auxiliary objective of the gated taggers, csrc/objective.hip). */
 #define ICKA_ABI_VERSION 6
 int icka_abi_version(void);
 const char* icka_build_arch(void);
@@ -413,6 +415,34 @@ int icka_dgelu_bf16(const void* dg, const void* z, void* dz, int64_t n, void* st
 /* dx = dy * (1 - y*y) (bf16, contiguous n elements): backward of the Tanh inside the prompt mapping networks
  * (Cross_Modal_Interaction_Module.py:914-928: Dropout, Linear, Tanh, Dropout, Linear). */
 int icka_tanh_bwd(const void* dy, const void* y, void* dx, int64_t n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Auxiliary training objective of the gated taggers (gate_cl_modeling.py:1276-1395, cl_modeling.py:1376-1382;
+ * csrc/objective.hip).  Arithmetic in f32; fixed-order reductions, no atomics: two runs are bitwise equal.
+ *
+ * Contrastive (InfoNCE) loss of text rows t [B, D] against image rows v [B, D] (row strides ldt / ldv in elements;
+ * dtype 0 = f32, 1 = bf16, 2 = fp16), 1 <= B <= 256, 8 <= D <= 4096, D % 8 == 0 (else ICKA_E_SHAPE):
+ *   s_ij = cos(t_i, v_j) / temp (no epsilon in the norms, as the reference),
+ *   stats[0] = (1/B) sum_i [temp_lamb (lse_j s_ij - s_ii) + (1 - temp_lamb)(lse_j s_ji - s_ii)].
+ * With crs (f32 [B, 2], nullable) the relevance cross-entropy of gate_cl rides along:
+ *   stats[1] = mean_b CE(crs_b, y_b), y_b = 0 for the last n_neg samples, 1 otherwise (0 when crs is null).
+ * One launch (one workgroup).  ws: icka_contrastive_workspace_floats(B) floats, read by the backward. */
+int64_t icka_contrastive_workspace_floats(int32_t B);
+int icka_contrastive_fwd(const void* t, int64_t ldt, const void* v, int64_t ldv, int32_t dtype, int32_t B, int32_t D,
+                         float temp, float temp_lamb, const float* crs, int32_t n_neg, float* stats, float* ws, void* stream);
+/* Gradient: dt, dv contiguous f32 [B, D] (whatever the input dtype) from the upstream gradients dcl[0] (of stats[0]) and dcrs_loss[0] (of
+ * stats[1]; read only with crs), both read from DEVICE memory (no host sync, capture-safe); dcrs f32 [B, 2] when crs is given.
+ * One launch of 2B workgroups. */
+int icka_contrastive_bwd(const void* t, int64_t ldt, const void* v, int64_t ldv, int32_t dtype, int32_t B, int32_t D,
+                         float temp, float temp_lamb, const float* ws, const float* dcl, const float* dcrs_loss, void* dt,
+                         void* dv, const float* crs, int32_t n_neg, float* dcrs, void* stream);
+/* dx = dy * [y > 0] over n contiguous elements, bf16 (is_f32 = 0) or f32: backward of the ReLU between the two Linears of each
+ * projection head (gate_cl_modeling.py:1387-1388).  dy == y == x gives the forward relu(x) of the fp32 mode. */
+int icka_relu_bwd(const void* dy, const void* y, void* dx, int64_t n, int32_t is_f32, void* stream);
+/* Negative-sample swap (gate_cl_modeling.py:1345-1356): y = x with samples b0 + i and b0 + h + i exchanged for i < h,
+ * b0 = B - n_neg, h = n_neg / 2 (an odd last sample stays).  x, y: B samples of sample_bytes each (a multiple of 16,
+ * 16-byte aligned, out of place).  The permutation is its own inverse: the backward is the same call on the gradient. */
+int icka_sample_swap(const void* x, void* y, int32_t B, int64_t sample_bytes, int32_t n_neg, void* stream);
 /* Token-level cross-entropy over valid tokens (benchmark loss), fused forward + backward:
  * logits f32 [M,C] (ld), labels/mask int64 [M]; loss_sum f32[1] += sum of -log p ; count f32[1] += #valid ;
  * dlogits bf16 [M, ldd] (ldd >= C, pad columns zeroed) = (softmax - onehot) * valid  (see icka_scale_by_ratio). */
