@@ -18,10 +18,13 @@ from . import graph
 from .graph import DevicePrefetcher, GraphedModule, GraphedStep
 from . import cross_modal
 from .cross_modal import PromptRobertaModel
+from . import packing
+from .packing import PackOverflowError, TokenBudgetBatchSampler, set_packed
 
 __all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "BertConfig", "BertModel", "BertEmbeddings", "BertEncoder", "BertLayer", "BertLayerNorm", "BertPooler",
            "BertSelfEncoder", "BertCrossEncoder", "BertCrossAttentionLayer", "BertAttention", "BertCrossAttention",
            "BertSelfAttention", "BertCoAttention", "BertSelfOutput", "BertIntermediate", "BertOutput",
            "BertPreTrainedModel", "MTCCMBertForMMTokenClassificationCRF", "cls_layer_both", "scalar_gate_fusion",
            "token_ce_loss", "set_precision", "resolved_precision", "ParamArena", "cross_modal", "PromptRobertaModel",
-           "GradReducer", "graph", "DevicePrefetcher", "GraphedModule", "GraphedStep"]
+           "GradReducer", "graph", "DevicePrefetcher", "GraphedModule", "GraphedStep", "packing", "set_packed",
+           "PackOverflowError", "TokenBudgetBatchSampler"]

@@ -169,6 +169,14 @@ PROTOTYPES = {
     "icka_bump_dropout_nonce": (c_i32, [c_vp, c_vp]),
     "icka_dropout_mask": (c_i32, [c_vp, c_i64, c_f32, c_u64, c_vp]),
     "icka_attn_dropout_mask": (c_i32, [c_vp, c_i64, c_i32, c_f32, c_u64, c_vp]),
+    # ---- packed batches (csrc/packed.hip, attention.hip)
+    "icka_pack_plan": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "icka_rows_gather": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, C.c_uint32, c_vp]),
+    "icka_attn_fwd_packed": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i64, c_i32,
+                                     c_i32, c_i32, c_i32, c_f32, c_f32, c_u64, c_vp, c_vp]),
+    "icka_attn_bwd_packed": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                     c_i64, c_vp, c_i64, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_u64,
+                                     c_vp, c_vp]),
     # ---- data-parallel helpers (csrc/dp.hip)
     "icka_dp_chunk_elems": (c_i64, []),
     "icka_dp_cast_chunks": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),

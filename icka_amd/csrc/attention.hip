@@ -449,9 +449,43 @@ __global__ void attn_keepbits_kernel(uint32_t* __restrict__ out, int64_t rows, i
     }
 }
 
-template <int QT, int KT, bool DROP, bool FP8 = false, bool KB = false>
+// ---- packed (padding-free) batches: the VL instances of the whole-head kernels below.  Sample b's queries are the rows
+// [cu[b], cu[b+1]) (AttnArgs::cu, read from device memory: one captured graph serves every batch); its keys are the same rows
+// (kv_packed, self-attention) or stay at b * Skv (text -> image cross-attention).  VL_FILL_BLOCKS extra blocks of each launch
+// write zeros to the filler rows [cu[B], Mrows) that belong to no sample, so that everything summed over all rows downstream
+// (weight gradients, bias column sums) reads defined values.
+constexpr int VL_FILL_BLOCKS = 16;
+struct VlRows { int64_t q0, kv0; int nq, nkv; };
+__device__ __forceinline__ VlRows vl_rows(const AttnArgs& a, int b) {
+    // clamped so that a corrupt row map can never address past Mrows or a sample past Sq / Skv
+    const int64_t M = a.Mrows;
+    int64_t r0 = a.cu[b], r1 = a.cu[b + 1];
+    r0 = r0 < 0 ? 0 : (r0 > M ? M : r0);
+    r1 = r1 < r0 ? r0 : (r1 > M ? M : r1);
+    const int n = (int)(r1 - r0 < a.Sq ? r1 - r0 : a.Sq);
+    VlRows v;
+    v.q0 = r0; v.nq = n;
+    v.kv0 = a.kv_packed ? r0 : (int64_t)b * a.Skv;
+    v.nkv = a.kv_packed ? (n < a.Skv ? n : a.Skv) : a.Skv;
+    return v;
+}
+// zero this launch's columns (heads * 64) of the filler rows [cu[B], Mrows) of a token-major matrix; fb = filler block index
+__device__ __forceinline__ void vl_zero_filler(const AttnArgs& a, bf16_t* base, int64_t ld, int fb, int tid) {
+    int64_t r0 = a.cu[a.B];
+    r0 = r0 < 0 ? 0 : (r0 > a.Mrows ? a.Mrows : r0);
+    const int cpr = a.h * HD / 8;   // 16-byte chunks per row
+    const int64_t n = (a.Mrows - r0) * cpr;
+    for (int64_t i = (int64_t)fb * 256 + tid; i < n; i += VL_FILL_BLOCKS * 256) {
+        const int64_t r = r0 + i / cpr;
+        const int c = (int)(i % cpr);
+        *reinterpret_cast<u32x4*>(base + r * ld + c * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
+template <int QT, int KT, bool DROP, bool FP8 = false, bool KB = false, bool VL = false>
 __global__ __launch_bounds__(256) void attn_fwd_small_kernel(const AttnArgs a_) {
     static_assert(DROP || !KB, "keep bits exist with dropout only");
+    static_assert(!(VL && FP8), "no fp8 form of the packed kernels");
     AttnArgs a = a_;
     a.drop = drop_resolve(a.drop);
     constexpr int QR = 64 * QT, KR = 16 * KT;
@@ -460,10 +494,29 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(const AttnArgs a_) 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int bh = blockIdx.x, head = bh % a.h, b = bh / a.h;
     const int q0 = blockIdx.y * QR;   // query block of this head (grid.y > 1 splits a head for load balance)
-    stage_rows<QR>(sQ, a.Q + ((int64_t)b * a.Sq + q0) * a.ldq + head * HD, a.ldq, a.Sq - q0, tid);
-    stage_rows<KR>(sK, a.K + (int64_t)b * a.Skv * a.ldk + head * HD, a.ldk, a.Skv, tid);
-    stage_rows<KR>(sV, a.V + (int64_t)b * a.Skv * a.ldv + head * HD, a.ldv, a.Skv, tid);
+    VlRows vr{};
+    if constexpr (VL) {
+        if (bh >= a.B * a.h) {
+            if (blockIdx.y == 0) vl_zero_filler(a, a.Ow, a.ldo, bh - a.B * a.h, tid);
+            return;
+        }
+        vr = vl_rows(a, b);
+        if (q0 >= vr.nq) return;      // (block-uniform: no barrier is skipped by part of the block)
+        stage_rows<QR>(sQ, a.Q + (vr.q0 + q0) * a.ldq + head * HD, a.ldq, vr.nq - q0, tid);
+        stage_rows<KR>(sK, a.K + vr.kv0 * a.ldk + head * HD, a.ldk, vr.nkv, tid);
+        stage_rows<KR>(sV, a.V + vr.kv0 * a.ldv + head * HD, a.ldv, vr.nkv, tid);
+    } else {
+        stage_rows<QR>(sQ, a.Q + ((int64_t)b * a.Sq + q0) * a.ldq + head * HD, a.ldq, a.Sq - q0, tid);
+        stage_rows<KR>(sK, a.K + (int64_t)b * a.Skv * a.ldk + head * HD, a.ldk, a.Skv, tid);
+        stage_rows<KR>(sV, a.V + (int64_t)b * a.Skv * a.ldv + head * HD, a.ldv, a.Skv, tid);
+    }
     __syncthreads();
+    if constexpr (VL) {
+        // 16-query sub-tiles wholly past the sample's length: no MFMA work (nothing follows that needs the wave)
+        if (q0 + 16 * QT * wave < vr.nq)
+            attn_fwd_whole_head<QT, KT, DROP, FP8, KB, true>(a, sQ, sK, sV, QT * wave, q0, bh, b, head, lane, vr.q0, vr.nq);
+        return;
+    }
     if (ICKA_ATTN_ABLATE == 2) {   // staging + stores only
         for (int i = 0; i < QR * 8 / 256; ++i) {
             const int q = tid + 256 * i, r = q >> 3, c = q & 7;
@@ -481,9 +534,10 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(const AttnArgs a_) 
 // the whole 512-register file per wave (Pd and dS of a wave's 64 queries x 256 keys stay packed in 256 registers), the
 // mask read from LDS instead of registers, and the phase-B exchange done in groups of NCH 64-key chunks that fit the
 // dead K/V region (the [QR x KR] matrix no longer does).
-template <int QT, int KT, bool DROP, bool KB = false>
+template <int QT, int KT, bool DROP, bool KB = false, bool VL = false>
 __global__ __launch_bounds__(256, (QT * KT >= 36 || QT >= 4 ? 1 : 2)) void attn_bwd_small_kernel(const AttnArgs a_) {
     static_assert(DROP || !KB, "keep bits exist with dropout only");
+    static_assert(!(VL && QT * KT >= 36), "packed batches: heads of up to 128 x 128");
     AttnArgs a = a_;
     a.drop = drop_resolve(a.drop);
     constexpr int QR = 64 * QT, KR = 16 * KT, KW = KT / 4;
@@ -505,11 +559,37 @@ __global__ __launch_bounds__(256, (QT * KT >= 36 || QT >= 4 ? 1 : 2)) void attn_
     const float* mb = a.mask + (int64_t)b * a.Skv;
     ATTN_RSTAMP(8);
     ATTN_STAMP(0);
-    stage_rows<QR>(sQ, a.Q + (int64_t)b * a.Sq * a.ldq + head * HD, a.ldq, a.Sq, tid);
-    stage_rows<QR>(sDO, a.dO + (int64_t)b * a.Sq * a.lddo + head * HD, a.lddo, a.Sq, tid);
-    stage_rows<KR>(sK, a.K + (int64_t)b * a.Skv * a.ldk + head * HD, a.ldk, a.Skv, tid);
-    stage_rows<KR>(sV, a.V + (int64_t)b * a.Skv * a.ldv + head * HD, a.ldv, a.Skv, tid);
-    if (tid < QR) s_lse[tid] = tid < a.Sq ? a.lse[(int64_t)bh * a.Sq + tid] : INFINITY;
+    // VL: qlim = the sample's query count (queries past it have lse = +inf: P = 0, they add exact zeros), rows at q_row0 / kv_row0
+    int qlim = a.Sq, kvlim = a.Skv;
+    int64_t q_row0 = (int64_t)b * a.Sq, kv_row0 = (int64_t)b * a.Skv;
+    if constexpr (VL) {
+        if (bh >= a.B * a.h) {
+            const int fb = bh - a.B * a.h;
+            vl_zero_filler(a, a.dQ, a.lddq, fb, tid);
+            if (a.kv_packed) {
+                vl_zero_filler(a, a.dK, a.lddk, fb, tid);
+                vl_zero_filler(a, a.dV, a.lddv, fb, tid);
+            }
+            return;
+        }
+        const VlRows vr = vl_rows(a, b);
+        qlim = vr.nq; kvlim = vr.nkv; q_row0 = vr.q0; kv_row0 = vr.kv0;
+        if (qlim == 0) {   // an empty (or dropped) sample: its own key rows (cross-attention) get zero gradients
+            if (!a.kv_packed) {
+                for (int i = tid; i < a.Skv * 8; i += 256) {
+                    const int r = i >> 3, c = i & 7;
+                    *reinterpret_cast<u32x4*>(a.dK + (kv_row0 + r) * a.lddk + head * HD + c * 8) = u32x4{0u, 0u, 0u, 0u};
+                    *reinterpret_cast<u32x4*>(a.dV + (kv_row0 + r) * a.lddv + head * HD + c * 8) = u32x4{0u, 0u, 0u, 0u};
+                }
+            }
+            return;
+        }
+    }
+    stage_rows<QR>(sQ, a.Q + q_row0 * a.ldq + head * HD, a.ldq, qlim, tid);
+    stage_rows<QR>(sDO, a.dO + q_row0 * a.lddo + head * HD, a.lddo, qlim, tid);
+    stage_rows<KR>(sK, a.K + kv_row0 * a.ldk + head * HD, a.ldk, kvlim, tid);
+    stage_rows<KR>(sV, a.V + kv_row0 * a.ldv + head * HD, a.ldv, kvlim, tid);
+    if (tid < QR) s_lse[tid] = tid < qlim ? a.lse[(int64_t)bh * a.Sq + tid] : INFINITY;
     if constexpr (MASK_LDS) {
         static_assert(KR <= 256, "one mask element per thread");
         if (tid < KR) s_mask[tid] = tid < a.Skv ? mb[tid] : -INFINITY;
@@ -517,7 +597,7 @@ __global__ __launch_bounds__(256, (QT * KT >= 36 || QT >= 4 ? 1 : 2)) void attn_
     ATTN_STAMP(1);
     __syncthreads();
     ATTN_STAMP(2);
-    if (ICKA_ATTN_ABLATE == 2) {   // staging + stores only
+    if (ICKA_ATTN_ABLATE == 2 && !VL) {   // staging + stores only
         for (int i = 0; i < QR * 8 / 256; ++i) {
             const int q = tid + 256 * i, r = q >> 3, c = q & 7;
             if (r < a.Sq) *reinterpret_cast<u32x4*>(a.dQ + ((int64_t)b * a.Sq + r) * a.lddq + head * HD + c * 8) =
@@ -565,9 +645,9 @@ __global__ __launch_bounds__(256, (QT * KT >= 36 || QT >= 4 ? 1 : 2)) void attn_
             const uint32_t hx = (idx_row + 2u * (uint32_t)g) * ICKA_HASH_C0 + a.drop.s0;
             uint32_t kbw[KBW];
             if constexpr (KB) {
-                const uint32_t* kp = a.keepbits + (((int64_t)bh * a.Sq + (q < a.Sq ? q : 0)) * 4 + g) * wpl;
+                const uint32_t* kp = a.keepbits + (((int64_t)bh * a.Sq + (q < qlim ? q : 0)) * 4 + g) * wpl;
 #pragma unroll
-                for (int w = 0; w < KBW; ++w) kbw[w] = (w < wpl && q < a.Sq) ? kp[w] : 0u;
+                for (int w = 0; w < KBW; ++w) kbw[w] = (w < wpl && q < qlim) ? kp[w] : 0u;
             }
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt) {
@@ -588,6 +668,13 @@ __global__ __launch_bounds__(256, (QT * KT >= 36 || QT >= 4 ? 1 : 2)) void attn_
 #pragma unroll
     for (int qi = 0; qi < QT; ++qi) {
         const int q = 16 * (QT * wave + qi) + i15;
+        if constexpr (VL) {
+            if (16 * (QT * wave + qi) >= qlim) {   // a sub-tile wholly past the sample: P = dS = 0 (what the MFMAs would give)
+#pragma unroll
+                for (int kt = 0; kt < KT; ++kt) pdp[qi][kt] = dsp[qi][kt] = u32x2{0u, 0u};
+                continue;
+            }
+        }
         const bf16x8 qf0 = frag_row(sQ, 16 * (QT * wave + qi), 0, lane), qf1 = frag_row(sQ, 16 * (QT * wave + qi), 1, lane);
         const bf16x8 do0 = frag_row(sDO, 16 * (QT * wave + qi), 0, lane), do1 = frag_row(sDO, 16 * (QT * wave + qi), 1, lane);
         const float lse_q = s_lse[q];
@@ -595,9 +682,9 @@ __global__ __launch_bounds__(256, (QT * KT >= 36 || QT >= 4 ? 1 : 2)) void attn_
         const uint32_t hx = (idx_row + 2u * (uint32_t)g) * ICKA_HASH_C0 + a.drop.s0;   // pair index base (see drop_pair)
         uint32_t kbw[KBW];
         if constexpr (KB && !DROP_BITS) {
-            const uint32_t* kp = a.keepbits + (((int64_t)bh * a.Sq + (q < a.Sq ? q : 0)) * 4 + g) * wpl;
+            const uint32_t* kp = a.keepbits + (((int64_t)bh * a.Sq + (q < qlim ? q : 0)) * 4 + g) * wpl;
 #pragma unroll
-            for (int w = 0; w < KBW; ++w) kbw[w] = (w < wpl && q < a.Sq) ? kp[w] : 0u;
+            for (int w = 0; w < KBW; ++w) kbw[w] = (w < wpl && q < qlim) ? kp[w] : 0u;
         }
         // P and dropout-masked dP of this query row block.  Large heads keep P bf16-packed (dS is rounded to bf16 for its
         // MFMA anyway; dP - delta, where the cancellation is, stays f32): 32 registers fewer at the 512-register cap
@@ -661,7 +748,7 @@ __global__ __launch_bounds__(256, (QT * KT >= 36 || QT >= 4 ? 1 : 2)) void attn_
         }
         dl += __shfl_xor(dl, 16, 64);
         dl += __shfl_xor(dl, 32, 64);
-        if (g == 0 && q < a.Sq) a.delta[(int64_t)bh * a.Sq + q] = dl;
+        if (g == 0 && q < qlim) a.delta[(int64_t)bh * a.Sq + q] = dl;
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
             f32x4 pk;
@@ -683,8 +770,8 @@ __global__ __launch_bounds__(256, (QT * KT >= 36 || QT >= 4 ? 1 : 2)) void attn_
                 acc[dt] = mfma16(frag_tr(sK, dt, ks, lane),
                                  join8(as_bf16x4(dsp[qi][2 * ks]), as_bf16x4(dsp[qi][2 * ks + 1])), acc[dt]);
         }
-        if (q < a.Sq) {
-            bf16_t* row = a.dQ + ((int64_t)b * a.Sq + q) * a.lddq + head * HD;
+        if (q < qlim) {
+            bf16_t* row = a.dQ + (q_row0 + q) * a.lddq + head * HD;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
                 *reinterpret_cast<u32x2*>(row + 16 * dt + 4 * g) = pack4(acc[dt][0], acc[dt][1], acc[dt][2], acc[dt][3]);
@@ -762,9 +849,9 @@ __global__ __launch_bounds__(256, (QT * KT >= 36 || QT >= 4 ? 1 : 2)) void attn_
         for (int j = 0; j < NCH; ++j) {
             const int kw = gi * NCH + j;
             const int key = 16 * (4 * NCH * gi + NCH * wave + j) + i15;
-            if (key < a.Skv) {
-                bf16_t* krow = a.dK + ((int64_t)b * a.Skv + key) * a.lddk + head * HD;
-                bf16_t* vrow = a.dV + ((int64_t)b * a.Skv + key) * a.lddv + head * HD;
+            if (key < kvlim) {
+                bf16_t* krow = a.dK + (kv_row0 + key) * a.lddk + head * HD;
+                bf16_t* vrow = a.dV + (kv_row0 + key) * a.lddv + head * HD;
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
                     *reinterpret_cast<u32x2*>(krow + 16 * dt + 4 * g) =
@@ -839,6 +926,33 @@ static bool try_small(const AttnArgs& a, int mode, hipStream_t st) {
     else if (k8) launch_small<1, 8>(a, mode, st);
     else launch_small<1, 4>(a, mode, st);
     return true;
+}
+
+// packed batches (heads of up to 128 x 128, bf16): the same instance as the padded launch of the same padded Sq / Skv, so that
+// every valid row is the padded kernel's arithmetic bit for bit; grid.x grows by the VL_FILL_BLOCKS filler blocks
+template <int QT, int KT, bool DROP, bool KB>
+static void launch_vl2(const AttnArgs& a, bool bwd, hipStream_t st) {
+    const int nb = a.B * a.h + VL_FILL_BLOCKS;
+    if (bwd) {
+        hipLaunchKernelGGL((attn_bwd_small_kernel<QT, KT, DROP, KB, true>), dim3(nb), dim3(256), 0, st, a);
+    } else if (QT == 2 && (a.B * a.h) % 256 != 0) {
+        hipLaunchKernelGGL((attn_fwd_small_kernel<1, KT, DROP, false, KB, true>), dim3(nb, 2), dim3(256), 0, st, a);
+    } else {
+        hipLaunchKernelGGL((attn_fwd_small_kernel<QT, KT, DROP, false, KB, true>), dim3(nb), dim3(256), 0, st, a);
+    }
+}
+template <int QT, int KT>
+static void launch_vl(const AttnArgs& a, bool bwd, hipStream_t st) {
+    if (a.drop.thr && a.keepbits) launch_vl2<QT, KT, true, true>(a, bwd, st);
+    else if (a.drop.thr) launch_vl2<QT, KT, true, false>(a, bwd, st);
+    else launch_vl2<QT, KT, false, false>(a, bwd, st);
+}
+static void try_vl(const AttnArgs& a, bool bwd, hipStream_t st) {
+    const bool q2 = a.Sq > 64, k8 = a.Skv > 64;
+    if (q2 && k8) launch_vl<2, 8>(a, bwd, st);
+    else if (q2) launch_vl<2, 4>(a, bwd, st);
+    else if (k8) launch_vl<1, 8>(a, bwd, st);
+    else launch_vl<1, 4>(a, bwd, st);
 }
 
 inline bool ok16(const void* p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 8 == 0; }
@@ -974,6 +1088,54 @@ extern "C" int icka_attn_bwd(const void* Q, int64_t ldq, const void* K, int64_t 
     }
     ICKA_CHECK_LAUNCH();
     hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(B * heads * ((Skv + TILE - 1) / TILE)), dim3(256), 0, st, a);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- packed (padding-free) batches: see icka_hip.h
+static int vl_check(int32_t B, int32_t heads, int32_t Sq, int32_t Skv, int32_t kv_packed, int64_t Mrows) {
+    if (B <= 0 || heads <= 0 || Sq <= 0 || Skv <= 0 || Sq > 128 || Skv > 128 || Mrows <= 0) return ICKA_E_SHAPE;
+    if (kv_packed && Skv != Sq) return ICKA_E_SHAPE;
+    if ((int64_t)B * heads * Sq * Skv >= (1ll << 32)) return ICKA_E_SHAPE;  // 32-bit dropout counter
+    return 0;
+}
+extern "C" int icka_attn_fwd_packed(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                                    const float* add_mask, void* O, int64_t ldo, float* lse, const int32_t* cu_seqlens,
+                                    int32_t kv_packed, int64_t Mrows, int32_t B, int32_t heads, int32_t Sq, int32_t Skv,
+                                    float scale, float p_drop, uint64_t seed, void* keep_bits, void* stream) {
+    if (!Q || !K || !V || !add_mask || !O || !cu_seqlens) return ICKA_E_ARG;
+    if (const int rc = vl_check(B, heads, Sq, Skv, kv_packed, Mrows)) return rc;
+    if (!ok16(Q, ldq) || !ok16(K, ldk) || !ok16(V, ldv) || !ok16(O, ldo)) return ICKA_E_ALIGN;
+    AttnArgs a{};
+    a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.V = (const bf16_t*)V; a.ldv = ldv;
+    a.mask = add_mask; a.Ow = (bf16_t*)O; a.ldo = ldo; a.lse = lse;
+    a.B = B; a.h = heads; a.Sq = Sq; a.Skv = Skv; a.scale = scale; a.drop = make_drop(p_drop, seed);
+    a.keepbits = a.drop.thr ? (uint32_t*)keep_bits : nullptr;
+    a.cu = cu_seqlens; a.kv_packed = kv_packed ? 1 : 0; a.Mrows = Mrows;
+    try_vl(a, false, (hipStream_t)stream);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int icka_attn_bwd_packed(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                                    const float* add_mask, const void* dO, int64_t lddo, const float* lse, float* delta,
+                                    void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv,
+                                    const int32_t* cu_seqlens, int32_t kv_packed, int64_t Mrows, int32_t B, int32_t heads,
+                                    int32_t Sq, int32_t Skv, float scale, float p_drop, uint64_t seed, const void* keep_bits,
+                                    void* stream) {
+    if (!Q || !K || !V || !add_mask || !dO || !lse || !delta || !dQ || !dK || !dV || !cu_seqlens) return ICKA_E_ARG;
+    if (const int rc = vl_check(B, heads, Sq, Skv, kv_packed, Mrows)) return rc;
+    if (!ok16(Q, ldq) || !ok16(K, ldk) || !ok16(V, ldv) || !ok16(dO, lddo) || !ok16(dQ, lddq) || !ok16(dK, lddk) ||
+        !ok16(dV, lddv))
+        return ICKA_E_ALIGN;
+    AttnArgs a{};
+    a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.V = (const bf16_t*)V; a.ldv = ldv;
+    a.mask = add_mask; a.dO = (const bf16_t*)dO; a.lddo = lddo;
+    a.lse = const_cast<float*>(lse); a.delta = delta;
+    a.dQ = (bf16_t*)dQ; a.lddq = lddq; a.dK = (bf16_t*)dK; a.lddk = lddk; a.dV = (bf16_t*)dV; a.lddv = lddv;
+    a.B = B; a.h = heads; a.Sq = Sq; a.Skv = Skv; a.scale = scale; a.drop = make_drop(p_drop, seed);
+    a.keepbits = a.drop.thr ? const_cast<uint32_t*>((const uint32_t*)keep_bits) : nullptr;
+    a.cu = cu_seqlens; a.kv_packed = kv_packed ? 1 : 0; a.Mrows = Mrows;
+    try_vl(a, true, (hipStream_t)stream);
     ICKA_CHECK_LAUNCH();
     return 0;
 }

@@ -59,6 +59,10 @@ struct AttnArgs {
     // backward instead of hashing again (the hash is about half of the backward's vector work per element): per (batch*head,
     // query, lane group g = (key % 16) / 4) WPL = ceil(Skv / 128) words, bit (key / 16) * 4 + key % 4 of the group's words
     uint32_t* keepbits;
+    // packed (padding-free) batches, whole-head kernels only: sample b's queries are the rows [cu[b], cu[b+1]) of Q / O / dO /
+    // dQ (and of K / V / dK / dV when kv_packed: self-attention); rows [cu[B], Mrows) belong to no sample and are written as
+    // zeros.  Masks, lse, delta, keep bits and the dropout hash keep their padded coordinates (b, head, query, key < Skv).
+    const int* cu; int kv_packed; int64_t Mrows;
 #ifdef ICKA_ATTN_STAMP
     unsigned long long* stamp;   // diagnostic build: [block][wave][16] s_memtime / s_memrealtime stamps (tools/attn_stamp.py)
 #endif
@@ -105,10 +109,12 @@ __host__ __device__ __forceinline__ int keep_wpl(int Skv) { return (Skv + 127) >
 // rows (at least 16 * (wq + QT) query rows, 16 * KT key rows); wq = index of the wave's first 16-query sub-tile inside sQ,
 // q0 = query index (inside the sample) of sQ's row 0; bh = batch * heads + head (dropout counter, lse / keep-bit rows).
 // a.drop must already be resolved (drop_resolve).  Writes the context rows (a.Ow / a.Ow16), a.lse and the keep bits.
-template <int QT, int KT, bool DROP, bool FP8, bool KB>
+// VL (packed batches): the context row of query q is obase + q and only queries q < nq are written.
+template <int QT, int KT, bool DROP, bool FP8, bool KB, bool VL = false>
 __device__ __forceinline__ void attn_fwd_whole_head(const AttnArgs& a, const char* sQ, const char* sK, const char* sV, int wq,
-                                                    int q0, int bh, int b, int head, int lane) {
+                                                    int q0, int bh, int b, int head, int lane, int64_t obase = 0, int nq = 0) {
     const int g = lane >> 4, i15 = lane & 15;
+    const int qlim = VL ? nq : a.Sq;
     const float* mb = a.mask + (int64_t)b * a.Skv;
     bf16x8 qf[QT][2];
 #pragma unroll
@@ -182,7 +188,7 @@ __device__ __forceinline__ void attn_fwd_whole_head(const AttnArgs& a, const cha
             }
         }
         if constexpr (KB) {
-            if (q < a.Sq) {
+            if (q < qlim) {
                 const int wpl = keep_wpl(a.Skv);
                 uint32_t* kp = a.keepbits + (((int64_t)bh * a.Sq + q) * 4 + g) * wpl;
 #pragma unroll
@@ -193,7 +199,7 @@ __device__ __forceinline__ void attn_fwd_whole_head(const AttnArgs& a, const cha
         psum += __shfl_xor(psum, 16, 64);
         psum += __shfl_xor(psum, 32, 64);
         inv[qi] = (FP8 ? 1.f / FP8_P_SCALE : 1.f) / psum;
-        if (g == 0 && a.lse && q < a.Sq) a.lse[(int64_t)bh * a.Sq + q] = mx + logf(psum);
+        if (g == 0 && a.lse && q < qlim) a.lse[(int64_t)bh * a.Sq + q] = mx + logf(psum);
 #pragma unroll
         for (int ks = 0; ks < KT / 2; ++ks) {
             if constexpr (FP8) {
@@ -226,15 +232,15 @@ __device__ __forceinline__ void attn_fwd_whole_head(const AttnArgs& a, const cha
 #pragma unroll
     for (int qi = 0; qi < QT; ++qi) {
         const int q = q0 + 16 * (wq + qi) + i15;
-        if (q < a.Sq) {
-            bf16_t* orow = a.Ow + ((int64_t)b * a.Sq + q) * a.ldo + head * HD;
+        if (q < qlim) {
+            bf16_t* orow = a.Ow + ((VL ? obase : (int64_t)b * a.Sq) + q) * a.ldo + head * HD;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
                 *reinterpret_cast<u32x2*>(orow + 16 * dt + 4 * g) =
                     pack4(acc[qi][dt][0] * inv[qi], acc[qi][dt][1] * inv[qi], acc[qi][dt][2] * inv[qi],
                           acc[qi][dt][3] * inv[qi]);
             if (a.Ow16) {   // (the context is a convex combination of value rows: no fp16 overflow beyond V's own range)
-                _Float16* hrow = a.Ow16 + ((int64_t)b * a.Sq + q) * a.ldo + head * HD;
+                _Float16* hrow = a.Ow16 + ((VL ? obase : (int64_t)b * a.Sq) + q) * a.ldo + head * HD;
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt)
                     *reinterpret_cast<f16x4*>(hrow + 16 * dt + 4 * g) =

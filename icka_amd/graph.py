@@ -62,6 +62,7 @@ from typing import Callable, Optional
 import torch
 
 from . import kernels as K
+from . import packing
 
 
 def _sig(values) -> tuple:
@@ -316,6 +317,7 @@ class _StepBase(object):
             self.arena.sync()
         K.lstm_check_error(self._detected)
         K.gemm_ln_check_error(self._detected)
+        packing.check_error(self.model, self._detected)   # a packed batch of an earlier replay that overflowed max_tokens
         if flags:
             K.dp_check_error(self._detected)
 
@@ -803,6 +805,7 @@ class GraphedModule(object):
         if reducer is None and accumulate != 1:
             raise ValueError("accumulate=k only changes WHEN gradients are exchanged: it needs reducer=")
         if reducer is not None:
+            packing.refuse(module, "GraphedModule(reducer=)")
             if not (reducer.is_cuda and reducer.backend == "nccl"):
                 raise RuntimeError("GraphedModule(reducer=) needs the nccl (= RCCL) backend on a ROCm device")
             if getattr(reducer, "sparse_word", None) is not None:
@@ -1002,6 +1005,7 @@ class SegmentedStep(_StepBase):
     _name = "SegmentedStep"
 
     def __init__(self, model: torch.nn.Module, step_fn: Callable[..., torch.Tensor], reducer, warmup: int = 3, inputs=None):
+        packing.refuse(model, "SegmentedStep")
         self._setup(model, step_fn, inputs)
         self.reducer = reducer
         self.segments = None
@@ -1187,6 +1191,7 @@ class FlaggedStep(_StepBase):
 
     def __init__(self, model: torch.nn.Module, step_fn: Callable[..., torch.Tensor], reducer, warmup: int = 3, inputs=None,
                  accumulate: int = 1):
+        packing.refuse(model, "FlaggedStep")
         if not (reducer.is_cuda and reducer.backend == "nccl"):
             raise RuntimeError("FlaggedStep needs the nccl (= RCCL) backend on a ROCm device")
         if accumulate < 1:
@@ -1314,6 +1319,8 @@ def build_step(model: torch.nn.Module, step_fn: Callable[..., torch.Tensor], inp
     (dp.all_ranks_agree); unless all ranks captured, all of them get ``dp.CaptureDisagreement`` and move to the next form
     together.  No rank ever builds another form than its peers (the reference has one code path per rank,
     My_cross_attention.py:653-657, :768-776)."""
+    if reducer is not None:
+        packing.refuse(model, "build_step(reducer=)")
     say = log or (lambda msg: None)
     if not graph:
         return step_fn, "eager"

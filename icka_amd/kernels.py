@@ -667,6 +667,120 @@ def attn_bwd(q, k, v, add_mask, out, dout, lse, delta, dq, dk, dv, B, heads, Sq,
                             _ptr(keepbits), _lib.ATTN_TILED if tiled else 0, _stream()), "icka_attn_bwd")
 
 
+# ------------------------------------------------------------------------------------------------- packed batches
+def _i32vec(t: torch.Tensor, n: int, name: str) -> None:
+    _dev(t, name)
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n:
+        raise ValueError("%s must be a contiguous int32 device tensor of at least %d elements" % (name, n))
+
+
+def pack_plan(mask: torch.Tensor, max_tokens: int, plan, err_word: int = 0) -> None:
+    """icka_pack_plan: input_mask (int64 [B,S]) -> the row maps of ``plan`` (packing.Plan: lens, cu, p2p, pad2pack, cls_of,
+    status).  ``err_word``: address of a host-mapped uint32[2] that receives {tokens, flags} on overflow (0: none)."""
+    _dev(mask, "mask")
+    if mask.dtype != torch.int64 or mask.dim() != 2 or not mask.is_contiguous():
+        raise ValueError("mask must be a contiguous int64 [B, S] tensor")
+    B, S = mask.shape
+    _i32vec(plan.lens, B, "lens")
+    _i32vec(plan.cu, B + 1, "cu_seqlens")
+    _i32vec(plan.p2p, max_tokens, "packed_to_padded")
+    _i32vec(plan.pad2pack, B * S, "padded_to_packed")
+    _i32vec(plan.cls_of, max_tokens, "cls_of")
+    if plan.status is not None:
+        _i32vec(plan.status, 2, "status")
+    check(_lib.load().icka_pack_plan(mask.data_ptr(), B, S, max_tokens, plan.lens.data_ptr(), plan.cu.data_ptr(),
+                                     plan.p2p.data_ptr(), plan.pad2pack.data_ptr(), plan.cls_of.data_ptr(), _ptr(plan.status),
+                                     err_word or None, _stream()), "icka_pack_plan")
+
+
+def rows_gather(src: torch.Tensor, dst: torch.Tensor, row_map: torch.Tensor, map_stride: int = 1, fill: int = 0) -> torch.Tensor:
+    """dst[r] = src[row_map[r * map_stride]] (-1: zeros, -2: every 32-bit word = ``fill``).  src / dst: 2-D row-major views of
+    one dtype whose rows are whole 32-bit words (bf16 with an even width, f32)."""
+    _dev(src, "src")
+    _dev(dst, "dst")
+    if src.dtype != dst.dtype or src.dim() != 2 or dst.dim() != 2 or src.shape[1] != dst.shape[1]:
+        raise ValueError("rows_gather: src and dst must be 2-D of one dtype and width")
+    es = src.element_size()
+    if (src.shape[1] * es) % 4 or src.stride(1) != 1 or dst.stride(1) != 1 or (src.stride(0) * es) % 4 or (dst.stride(0) * es) % 4:
+        raise ValueError("rows_gather: rows must be whole 32-bit words of a row-major view")
+    _dev(row_map, "row_map")
+    if row_map.dtype != torch.int32 or not row_map.is_contiguous() or row_map.numel() < (dst.shape[0] - 1) * map_stride + 1:
+        raise ValueError("rows_gather: row_map must be a contiguous int32 tensor covering every destination row")
+    words = src.shape[1] * es // 4
+    ld_s = src.stride(0) * es // 4
+    ld_d = dst.stride(0) * es // 4
+    check(_lib.load().icka_rows_gather(src.data_ptr(), ld_s, src.shape[0], dst.data_ptr(), ld_d, dst.shape[0], words,
+                                       row_map.data_ptr(), map_stride, fill, _stream()), "icka_rows_gather")
+    return dst
+
+
+def _f32vec(t, n: int, name: str) -> None:
+    if t is None:
+        return
+    _dev(t, name)
+    if t.dtype != F32 or not t.is_contiguous() or t.numel() < n:
+        raise ValueError("%s must be a contiguous f32 device tensor of at least %d elements" % (name, n))
+
+
+def _packed_checks(B, heads, Sq, Skv, M, kv_packed, add_mask, cu, **mats) -> None:
+    """Row counts and widths of the operands of the packed attention calls: the query-side matrices (and the key-side ones when
+    ``kv_packed``) hold at least Mrows rows, the key-side ones of a cross-attention at least B * Skv; every one at least
+    heads * 64 columns; add_mask is contiguous f32 [B, Skv]."""
+    _i32vec(cu, B + 1, "cu_seqlens")
+    if not (0 < Sq <= 128 and 0 < Skv <= 128) or (kv_packed and Skv != Sq) or M <= 0:
+        raise ValueError("packed attention: Sq, Skv in [1, 128] (equal for self-attention) and at least one packed row")
+    _dev(add_mask, "add_mask")
+    if add_mask.dtype != F32 or not add_mask.is_contiguous() or add_mask.numel() != B * Skv:
+        raise ValueError("add_mask must be contiguous f32 [B, Skv] = [%d, %d]" % (B, Skv))
+    for n, t in mats.items():
+        key_side = n in ("k", "v", "dk", "dv")
+        rows = B * Skv if (key_side and not kv_packed) else M
+        if t.shape[0] < rows:
+            raise ValueError("%s must hold at least %d rows, got %d" % (n, rows, t.shape[0]))
+        if t.shape[1] < heads * 64:
+            raise ValueError("%s must hold at least heads * 64 = %d columns, got %d" % (n, heads * 64, t.shape[1]))
+
+
+def attn_fwd_packed(q, k, v, add_mask, out, lse, cu, kv_packed: bool, B, heads, Sq, Skv, *, p_drop=0.0, seed=0, scale=None,
+                    keepbits=None):
+    """attn_fwd for packed queries (icka_attn_fwd_packed): q / out rows are the packed rows [cu[b], cu[b+1]) of sample b; k / v
+    too when ``kv_packed`` (self-attention), else at b * Skv.  Sq / Skv are the PADDED lengths (<= 128)."""
+    lib = _lib.load()
+    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _mat(t, n)
+    M = out.shape[0]        # Mrows: the kernel clamps cu_seqlens to it and reads / writes packed rows below it only
+    _packed_checks(B, heads, Sq, Skv, M, kv_packed, add_mask, cu, q=q, out=out, k=k, v=v)
+    _f32vec(lse, B * heads * Sq, "lse")
+    if keepbits is not None and (not keepbits.is_cuda or keepbits.element_size() != 4 or not keepbits.is_contiguous()
+                                 or keepbits.numel() < lib.icka_attn_keepbits_words(B, heads, Sq, Skv)):
+        raise ValueError("keepbits: contiguous 32-bit device buffer of icka_attn_keepbits_words words (attn_keepbits)")
+    check(lib.icka_attn_fwd_packed(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                                   add_mask.data_ptr(), out.data_ptr(), out.stride(0), _ptr(lse), cu.data_ptr(), int(kv_packed),
+                                   out.shape[0], B, heads, Sq, Skv, (1.0 / 8.0) if scale is None else scale, p_drop, seed,
+                                   _ptr(keepbits), _stream()), "icka_attn_fwd_packed")
+    return out
+
+
+def attn_bwd_packed(q, k, v, add_mask, dout, lse, delta, dq, dk, dv, cu, kv_packed: bool, B, heads, Sq, Skv, *, p_drop=0.0,
+                    seed=0, scale=None, keepbits=None):
+    lib = _lib.load()
+    for n, t in (("q", q), ("k", k), ("v", v), ("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
+        _mat(t, n)
+    M = dq.shape[0]         # Mrows (see attn_fwd_packed)
+    _packed_checks(B, heads, Sq, Skv, M, kv_packed, add_mask, cu, q=q, dout=dout, dq=dq, k=k, v=v, dk=dk, dv=dv)
+    _f32vec(lse, B * heads * Sq, "lse")
+    _f32vec(delta, B * heads * Sq, "delta")
+    if keepbits is not None and (not keepbits.is_cuda or keepbits.element_size() != 4 or not keepbits.is_contiguous()
+                                 or keepbits.numel() < lib.icka_attn_keepbits_words(B, heads, Sq, Skv)):
+        raise ValueError("keepbits: contiguous 32-bit device buffer of icka_attn_keepbits_words words (attn_keepbits)")
+    check(lib.icka_attn_bwd_packed(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                                   add_mask.data_ptr(), dout.data_ptr(), dout.stride(0), lse.data_ptr(), delta.data_ptr(),
+                                   dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0),
+                                   cu.data_ptr(), int(kv_packed), dq.shape[0], B, heads, Sq, Skv,
+                                   (1.0 / 8.0) if scale is None else scale, p_drop, seed, _ptr(keepbits), _stream()),
+          "icka_attn_bwd_packed")
+
+
 # ------------------------------------------------------------------------------------------------- LSTM
 def lstm_fwd(gates_x, w_hh, y, c_all, act, hprev, B, S, H, flags=0):
     """gates_x f32 [B*S, 8H]; w_hh bf16 [8H, H] (= [2][4H][H]); y bf16 [B*S, 2H]; c_all f32 [B*S, 2H];

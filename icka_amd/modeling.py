@@ -21,6 +21,7 @@ import torch.nn as nn
 from . import exact as X
 from . import kernels as K
 from . import ops
+from . import packing
 from .arena import ArenaModule, ParamArena, arena_of, refresh_shadow_once
 from .config import BertConfig, check_config, check_head_size_bf16
 
@@ -629,12 +630,47 @@ class BertModel(BertPreTrainedModel):
         return encoded_layers, pooled_output
 
 
-def _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att, pool=False):
+def _packed_text_encoder(self, A, plan, input_ids, segment_ids, input_mask, pool):
+    """Text encoder of a packed batch (packing.set_packed): the embeddings run padded, their rows (and f32 twin) are gathered
+    into the plan's max_tokens rows, the encoder layers run on those rows with the varlen attention kernels.  Returns
+    (seq bf16 [T,H], its f32 twin or None, pooled [B,H] or None); the pooler reads the first row of every sample."""
+    cfg = self.config
+    B, S = input_ids.shape
+    H, T = cfg.hidden_size, plan.max_tokens
+    dev = input_ids.device
+    add_mask = K.additive_mask(input_mask if input_mask.dtype == torch.int64 else input_mask.long(), S,
+                               torch.empty(B, S, dtype=F32, device=dev))
+    emb = self.bert.embeddings(input_ids, segment_ids)
+    embf = _twin(emb)
+    x = packing.RowsGatherFn.apply(emb.view(B * S, H), plan.p2p, 1, T, plan.pad2pack, 1)
+    xf = None
+    if embf is not None:   # the forward twin is not differentiable: gathered outside autograd
+        xf = K.rows_gather(embf, torch.empty(T, H, dtype=embf.dtype, device=dev), plan.p2p)
+    d = _dims(cfg, B, S, 0, self.training)
+    d.pack = plan
+    for layer in self.bert.encoder.layer:
+        x, xf = ops.BertLayerFn.apply(A.anchor, x, xf, layer, A, add_mask, d)
+    pooled = None
+    if pool:
+        if torch.is_grad_enabled() and x.requires_grad:
+            to_pool, x = ops.FanOutFn.apply(x, 2)
+        else:
+            to_pool = x
+        # row cu[b] of every sample (padded_to_packed at b*S); the backward puts dpooled back through cls_of.  An empty sample
+        # has no packed row: its pooler input is a zero row (the padded path reads the encoder output at its position 0), so
+        # aux_losses batches must not be filled up with empty samples (packing.set_packed)
+        first = packing.RowsGatherFn.apply(to_pool, plan.pad2pack, S, B, plan.cls_of, 1)
+        pooled = ops.LinearFn.apply(A.anchor, first, self.bert.pooler.dense, A, False, K.EPI_TANH)
+    return x, xf, pooled
+
+
+def _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att, pool=False, plan=None):
     """Shared trunk of the MNER heads: BERT text encoder -> dropout -> region tokens -> vismap2text -> text->image cross
     encoder (cl_modeling.py:1341-1361 = Cross_Modal_Interaction_Module.py:949-969 / :2446-2466).  ``self`` provides
     ``config, bert, vismap2text, txt2img_attention``.  Returns (arena, seq bf16 [B*S,H], its f32 twin or None,
     cross bf16 [B*S,H], its f32 twin), followed by the pooled output [B,H] of the last encoder layer, taken before the
-    dropout (gate_cl_modeling.py:1322-1326), when ``pool``."""
+    dropout (gate_cl_modeling.py:1322-1326), when ``pool``.  ``plan`` (packing.Plan): a packed batch -- seq / cross are then the
+    plan's max_tokens rows."""
     cfg = self.config
     B, S = input_ids.shape
     H = cfg.hidden_size
@@ -642,7 +678,10 @@ def _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, 
     dev = input_ids.device
     # ---- text encoder (cl_modeling.py:1341-1344)
     pooled = None
-    if isinstance(self.bert, BertModel):
+    if plan is not None:
+        seq, seqf, pooled = _packed_text_encoder(self, A, plan, input_ids, segment_ids, input_mask, pool)
+        sequence_output = None
+    elif isinstance(self.bert, BertModel):
         sequence_output = self.bert.encode(input_ids, segment_ids, input_mask, output_all_encoded_layers=False)[-1]
         if pool:
             # the last layer feeds the pooler and the head: one fan-out node sums the two gradients (as for seq below)
@@ -661,8 +700,9 @@ def _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, 
     if exact:
         return _mner_trunk_exact(self, A, sequence_output.view(B * S, H), added_attention_mask, visual_embeds_att, B,
                                  S) + tail
-    seq = sequence_output.view(B * S, H)
-    seqf = _twin(sequence_output)
+    if plan is None:
+        seq = sequence_output.view(B * S, H)
+        seqf = _twin(sequence_output)
     if self.training and cfg.hidden_dropout_prob > 0:
         seq = ops.DropoutFn.apply(seq, A, float(cfg.hidden_dropout_prob))
         seqf = None
@@ -701,6 +741,7 @@ def _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, 
     crossf = seqf
     for layer in self.txt2img_attention.layer:
         d = _dims(cfg, B, S, R, self.training, mixed=_is_mixed(layer))
+        d.pack = plan
         cross, crossf = ops.CrossLayerFn.apply(A.anchor, cross, crossf, vis, layer, A, img_mask, d,
                                                vis16 if d.h16 else None)
     return (A, seq, seqf, cross, crossf) + tail
@@ -802,7 +843,14 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
         cfg = self.config
         B, S = input_ids.shape
         H = cfg.hidden_size
-        trunk = _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att, pool=pool)
+        plan = None
+        st = packing.state_of(self)
+        if st is not None:   # packed token-budget batch (packing.set_packed)
+            st.check_error("detected at the next forward")
+            packing.validate(self, S)
+            plan = st.plan(input_mask)
+        trunk = _mner_trunk(self, input_ids, segment_ids, input_mask, added_attention_mask, visual_embeds_att, pool=pool,
+                            plan=plan)
         A, seq, seqf, cross, crossf = trunk[:5]
         pooled = trunk[5] if pool else None
         crs = None
@@ -845,6 +893,8 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
             seq16 = ops._fwd_twin(A, seq, seqf, d16)
             cross16 = ops._fwd_twin(A, cross, crossf, d16)
         logits = ops.GatedHeadFn.apply(A.anchor, seq, cross, self, A, seq16, cross16)
+        if plan is not None:   # back to [B*S, C]: pads exactly 0, valid tokens that were not packed (overflow) NaN
+            logits = packing.RowsGatherFn.apply(logits, plan.pad2pack, 1, B * S, plan.p2p, 1, packing.F32_NAN_WORD)
         return logits.view(B, S, self.num_labels), crs, pooled
 
     def forward(self, input_ids, segment_ids=None, input_mask=None, added_attention_mask=None, visual_embeds_mean=None,

@@ -58,9 +58,9 @@ def _c(t: torch.Tensor) -> torch.Tensor:
 
 class Dims(object):
     """Static description of one call: batch, query length, kv length, sizes, dropout probabilities."""
-    __slots__ = ("B", "S", "R", "H", "I", "heads", "eps", "p_hidden", "p_attn", "train", "h16")
+    __slots__ = ("B", "S", "R", "H", "I", "heads", "eps", "p_hidden", "p_attn", "train", "h16", "pack")
 
-    def __init__(self, B, S, R, H, I, heads, eps, p_hidden, p_attn, train, h16=False):
+    def __init__(self, B, S, R, H, I, heads, eps, p_hidden, p_attn, train, h16=False, pack=None):
         self.B, self.S, self.R, self.H, self.I, self.heads, self.eps = B, S, R, H, I, heads, eps
         self.p_hidden = p_hidden if train else 0.0
         self.p_attn = p_attn if train else 0.0
@@ -68,6 +68,9 @@ class Dims(object):
         # "mixed16": the forward GEMMs of the encoder layers read fp16 operands (activations: the fp16 twin that is also the
         # residual stream; weights: the arena's fp16 shadow); backward stays on the bf16 copies
         self.h16 = bool(h16)
+        # packed batches (packing.Plan or None): the text rows are the packed rows of the plan, the attention cores take the
+        # varlen kernels with its cu_seqlens
+        self.pack = pack
 
 
 def _fwd_twin(A: ParamArena, x, xf, d: Dims):
@@ -209,7 +212,7 @@ def _attn_core_fwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
         bq = A.f_cat((sa.query.bias, sa.key.bias, sa.value.bias))
         pre = None
         want_kb = save and d.p_attn > 0 and _keepbits_on(d.S, Skv)
-        if (FUSE_QKV_ATTN and d.S in (128, 256) and Skv == d.S and H == 64 * d.heads and M >= FUSE_QKV_ATTN_MIN_ROWS
+        if (FUSE_QKV_ATTN and d.pack is None and d.S in (128, 256) and Skv == d.S and H == 64 * d.heads and M >= FUSE_QKV_ATTN_MIN_ROWS
                 and not (want_kb and d.S != 256)):
             # projection + whole-head attention in ONE launch (icka_gemm_qkv_attn): every 256 x 192 tile = 256 / S samples x one
             # head's q | k | v, the attention runs from the tile's LDS images; bitwise the two launches below
@@ -253,6 +256,10 @@ def _attn_core_fwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
     # optional (ATTN_KEEPBITS): the forward leaves the keep decisions of its probability dropout as bits and the backward reads
     # them instead of hashing every (query, key) element a second time
     kb = pre[4] if pre else (K.attn_keepbits(d.B, d.heads, d.S, Skv, x.device) if (save and d.p_attn > 0 and _keepbits_on(d.S, Skv)) else None)
+    if d.pack is not None:   # packed batch: the varlen whole-head kernels (queries at the plan's rows; filler rows -> 0)
+        K.attn_fwd_packed(q, k, v, add_mask, ctx, lse, d.pack.cu, kv_src is None, d.B, d.heads, d.S, Skv, p_drop=d.p_attn,
+                          seed=seed_a, keepbits=kb)
+        return ctx, ctx16, ((qkv, kvbuf, lse, seed_a, kb) if save else None)
     K.attn_fwd(q, k, v, add_mask, ctx, lse, d.B, d.heads, d.S, Skv, p_drop=d.p_attn, seed=seed_a, fp8=fp8, out16=ctx16,
                keepbits=kb)
     return ctx, ctx16, ((qkv, kvbuf, lse, seed_a, kb) if save else None)
@@ -270,6 +277,9 @@ def _attn_core_bwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
         q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
         if generic:
             _attn_generic_bwd(lse, True, dctx, d, Skv, seed_a, dqkv, None)
+        elif d.pack is not None:
+            K.attn_bwd_packed(q, k, v, add_mask, dctx, lse, delta, dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:], d.pack.cu,
+                              True, d.B, d.heads, d.S, Skv, p_drop=d.p_attn, seed=seed_a, keepbits=kb)
         else:
             K.attn_bwd(q, k, v, add_mask, ctx, dctx, lse, delta, dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:], d.B,
                        d.heads, d.S, Skv, p_drop=d.p_attn, seed=seed_a, keepbits=kb)
@@ -285,6 +295,9 @@ def _attn_core_bwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
         K.zero_rows_(dkv, d.B * Skv)
     if generic:
         _attn_generic_bwd(lse, False, dctx, d, Skv, seed_a, dq, dkv)
+    elif d.pack is not None:
+        K.attn_bwd_packed(qkv, kvbuf[:, :H], kvbuf[:, H:], add_mask, dctx, lse, delta, dq, dkv[:, :H], dkv[:, H:], d.pack.cu,
+                          False, d.B, d.heads, d.S, Skv, p_drop=d.p_attn, seed=seed_a, keepbits=kb)
     else:
         K.attn_bwd(qkv, kvbuf[:, :H], kvbuf[:, H:], add_mask, ctx, dctx, lse, delta, dq, dkv[:, :H], dkv[:, H:], d.B,
                    d.heads, d.S, Skv, p_drop=d.p_attn, seed=seed_a, keepbits=kb)

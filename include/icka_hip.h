@@ -331,6 +331,44 @@ int icka_attn_bwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const 
                   int32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Packed (padding-free) batches, csrc/packed.hip + the varlen instances of the whole-head attention kernels.  The valid
+ * tokens of B samples occupy max_tokens rows: sample b the rows [cu_seqlens[b], cu_seqlens[b+1]); rows from cu_seqlens[B] on
+ * are filler rows that belong to no sample.
+ *
+ * icka_pack_plan: ONE launch from input_mask (int64 [B,S], B <= 2048, S <= 1024; a prefix mask, pos < len, per sample) to
+ *   lens [B] (int32, the prefix length of each mask), cu_seqlens [B+1] (int32), packed_to_padded [max_tokens] (b*S + s, -1
+ *   for filler rows), padded_to_packed [B*S] (-1 for pads, -2 for a valid token that was not packed), cls_of [max_tokens]
+ *   (b for the first row of sample b, else -1) and status (device int32[2] or NULL: total valid tokens, flags).  Samples
+ *   from the first one whose rows would end past max_tokens are dropped (length 0 in cu_seqlens); flags bit 0 = overflow,
+ *   bit 1 = a mask that is not a prefix mask.  On either, err_word (host-mapped uint32[2] or NULL) receives {tokens, flags}
+ *   with a system-scope store; nothing clears it on the device.
+ * icka_rows_gather: dst row r (r < dst_rows) = src row map[r * map_stride]; map entry -1 -> zeros, -2 -> every 32-bit word
+ *   = fill (a NaN pattern marks dropped tokens), entries >= src_rows read as -1.  Rows are row_words 32-bit words (bf16:
+ *   two elements a word; f32 logits: one); ld_* in words.  Packing, unpacking and both backwards are gathers through
+ *   one of the two maps: every destination row is written exactly once, no atomics.
+ * icka_attn_fwd_packed / icka_attn_bwd_packed: icka_attn_fwd_ex / icka_attn_bwd (bf16, whole-head, Sq <= 128 and Skv <= 128
+ *   padded lengths) for packed queries: the rows of Q / O / dO / dQ are the packed rows; K / V / dK / dV are too when
+ *   kv_packed (self-attention, Skv == Sq), else they stay at b*Skv + key (text -> image cross-attention).  cu_seqlens is read
+ *   on the device (one graph capture serves any batch).  add_mask [B,Skv], lse / delta [B,heads,Sq], keep_bits and the
+ *   dropout counters keep the PADDED coordinates, so every valid row equals the padded kernels' result bit for bit.
+ *   Filler rows [cu_seqlens[B], Mrows) of O (forward) and of dQ (and dK / dV when kv_packed) are written as zeros; the
+ *   backward zeroes dK / dV of the key rows of a sample with no packed query. */
+int icka_pack_plan(const int64_t* mask, int32_t B, int32_t S, int32_t max_tokens, int32_t* lens, int32_t* cu_seqlens,
+                   int32_t* packed_to_padded, int32_t* padded_to_packed, int32_t* cls_of, int32_t* status, void* err_word,
+                   void* stream);
+int icka_rows_gather(const void* src, int64_t ld_src, int64_t src_rows, void* dst, int64_t ld_dst, int64_t dst_rows,
+                     int32_t row_words, const int32_t* map, int64_t map_stride, uint32_t fill, void* stream);
+int icka_attn_fwd_packed(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                         const float* add_mask, void* O, int64_t ldo, float* lse, const int32_t* cu_seqlens, int32_t kv_packed,
+                         int64_t Mrows, int32_t B, int32_t heads, int32_t Sq, int32_t Skv, float scale, float p_drop,
+                         uint64_t seed, void* keep_bits, void* stream);
+int icka_attn_bwd_packed(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                         const float* add_mask, const void* dO, int64_t lddo, const float* lse, float* delta, void* dQ,
+                         int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int32_t* cu_seqlens,
+                         int32_t kv_packed, int64_t Mrows, int32_t B, int32_t heads, int32_t Sq, int32_t Skv, float scale,
+                         float p_drop, uint64_t seed, const void* keep_bits, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Element-wise / layout helpers.
  */
 /* fp32 -> bf16 cast of a flat buffer (parameter shadow refresh); n elements. */
