@@ -9,7 +9,9 @@ pytorch-crf 0.7.2 (the package is third-party and absent from the reference tree
 oracle/crf_oracle.py)."""
 from __future__ import annotations
 
-from typing import List, Optional
+import contextlib
+import threading
+from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -18,6 +20,84 @@ from . import kernels as K
 from .arena import ArenaModule, ParamArena, arena_of
 
 F32 = torch.float32
+_state = threading.local()
+
+
+@contextlib.contextmanager
+def device_decode():
+    """While active (on this thread), ``CRF.decode`` and ``CRF.decode_llh`` return a ``DeviceTags`` instead of python lists:
+    one launch, no host sync, so the call can be captured in a graph.  ``graph.GraphedModule(..., decode=True)`` sets it around
+    the calls it captures and replays."""
+    prev = getattr(_state, "on", False)
+    _state.on = True
+    try:
+        yield
+    finally:
+        _state.on = prev
+
+
+def device_decode_active() -> bool:
+    return getattr(_state, "on", False)
+
+
+def split_tags(lens: Sequence[int], flat: Sequence[int]) -> List[List[int]]:
+    """Cut the back-to-back paths ``flat`` into one list per sample of ``lens[b]`` tags."""
+    out, o = [], 0
+    for n in lens:
+        n = int(n)
+        if n < 0 or o + n > len(flat):
+            raise ValueError("path lengths %s do not fit %d tags" % (list(lens), len(flat)))
+        out.append(list(flat[o:o + n]))
+        o += n
+    return out
+
+
+class DeviceTags(object):
+    """Viterbi paths kept on the device (``icka_crf_score_decode``): ``lens`` int32 [B] and ``tags_flat`` int32 [>= B*S], the
+    paths back to back.  ``tolist()`` gives what ``CRF.decode`` returns.  ``DeviceTags.empty`` puts both in one buffer so that
+    ``tolist()`` is one device-to-host copy."""
+
+    def __init__(self, lens: torch.Tensor, tags_flat: torch.Tensor, _joint: Optional[torch.Tensor] = None):
+        for n, t in (("lens", lens), ("tags_flat", tags_flat)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("DeviceTags: %s must be a tensor, got %s" % (n, type(t).__name__))
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError("DeviceTags: %s must be a contiguous 1-D int32 tensor, got %s %s"
+                                 % (n, t.dtype, tuple(t.shape)))
+        if lens.device != tags_flat.device:
+            raise ValueError("DeviceTags: lens on %s, tags_flat on %s" % (lens.device, tags_flat.device))
+        self.lens = lens
+        self.tags_flat = tags_flat
+        self._joint = _joint
+
+    @classmethod
+    def empty(cls, B: int, S: int, device) -> "DeviceTags":
+        buf = torch.empty(B + B * S, dtype=torch.int32, device=device)
+        return cls(buf[:B], buf[B:], _joint=buf)
+
+    @property
+    def batch_size(self) -> int:
+        return self.lens.numel()
+
+    @property
+    def capacity(self) -> int:
+        return self.tags_flat.numel()
+
+    def check(self, B: int, S: int) -> None:
+        """Raise unless this can hold the paths of a [B, S] batch."""
+        K.check_flat_tags(self.lens, self.tags_flat, B, S)
+
+    def tolist(self) -> List[List[int]]:
+        if self._joint is not None:
+            h = self._joint.cpu().tolist()
+            B = self.batch_size
+            lens, flat = h[:B], h[B:]
+        else:
+            lens, flat = self.lens.cpu().tolist(), self.tags_flat.cpu().tolist()
+        return split_tags(lens, flat)
+
+    def __repr__(self) -> str:
+        return "DeviceTags(batch=%d, capacity=%d, device=%s)" % (self.batch_size, self.capacity, self.lens.device)
 
 
 class _CrfFn(torch.autograd.Function):
@@ -103,6 +183,10 @@ class CRF(ArenaModule):
         e, t, m = self._prep(emissions, tags, mask)
         A = self._arena()
         llh = _CrfFn.apply(A.anchor, e, t, m, self, A)
+        return self._reduce(llh, m, e, reduction)
+
+    @staticmethod
+    def _reduce(llh: torch.Tensor, m: Optional[torch.Tensor], e: torch.Tensor, reduction: str) -> torch.Tensor:
         if reduction == "none":
             return llh
         if reduction == "sum":
@@ -112,8 +196,37 @@ class CRF(ArenaModule):
         n = m.to(F32).sum() if m is not None else float(e.shape[0] * e.shape[1])
         return llh.sum() / n
 
-    def decode(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None) -> List[List[int]]:
-        """Most likely tag sequence per sample (Viterbi), as python lists of length sum(mask)."""
+    def _score_decode(self, e, t, m, out: Optional[DeviceTags]):
+        B, S = e.shape[0], e.shape[1]
+        if out is None:
+            out = DeviceTags.empty(B, S, e.device)
+        out.check(B, S)
+        llh = torch.empty(B, dtype=F32, device=e.device) if t is not None else None
+        self._arena()
+        K.crf_score_decode(e, t, m, self.start_transitions.detach(), self.end_transitions.detach(),
+                           self.transitions.detach(), llh, out.lens, out.tags_flat)
+        return out, llh
+
+    def decode_llh(self, emissions: torch.Tensor, tags: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                   reduction: str = "sum"):
+        """``(self.decode(emissions, mask), self(emissions, tags, mask, reduction))`` -- the dev pass of the reference.  Under
+        ``device_decode()`` (and without autograd to feed) both come from ONE launch: ``(DeviceTags, llh)``, the llh bit for
+        bit the forward's."""
+        if reduction not in ("none", "sum", "mean", "token_mean"):
+            raise ValueError("invalid reduction: %s" % reduction)
+        if not device_decode_active() or (torch.is_grad_enabled() and
+                                          (emissions.requires_grad or self.transitions.requires_grad)):
+            return self.decode(emissions, mask), self(emissions, tags, mask, reduction)
+        e, t, m = self._prep(emissions.detach(), tags, mask)
+        out, llh = self._score_decode(e, t, m, None)
+        return out, self._reduce(llh, m, e, reduction)
+
+    def decode(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None, out: Optional[DeviceTags] = None):
+        """Most likely tag sequence per sample (Viterbi), as python lists of length sum(mask).  Under ``device_decode()``, or
+        given ``out``, a ``DeviceTags`` (written into ``out`` when given) instead."""
+        if out is not None or device_decode_active():
+            e, _, m = self._prep(emissions.detach(), None, mask)
+            return self._score_decode(e, None, m, out)[0]
         e, _, m = self._prep(emissions.detach(), None, mask)
         self._arena()
         best = torch.empty(e.shape[0], e.shape[1], dtype=torch.int64, device=e.device)

@@ -75,9 +75,7 @@ __device__ __forceinline__ float gold_score(const CrfArgs& a, int b, int lane) {
 }
 
 // ------------------------------------------------------------------------------------------------ log-likelihood
-__global__ __launch_bounds__(64) void crf_llh_kernel(const CrfArgs a) {
-    __shared__ float s_T[64 * 64];
-    __shared__ float s_alpha[64];
+__device__ __forceinline__ void crf_llh_body(const CrfArgs& a, float* s_T, float* s_alpha) {
     const int b = blockIdx.x, j = threadIdx.x, C = a.C;
     for (int i = j; i < C * C; i += 64) s_T[i] = a.trans[i];
     const float num = gold_score(a, b, j);
@@ -94,6 +92,12 @@ __global__ __launch_bounds__(64) void crf_llh_kernel(const CrfArgs a) {
     const float m = wave_max(v);
     const float z = m + __logf(wave_sum(j < C ? __expf(v - m) : 0.f));
     if (j == 0) a.llh[b] = num - z;
+}
+
+__global__ __launch_bounds__(64) void crf_llh_kernel(const CrfArgs a) {
+    __shared__ float s_T[64 * 64];
+    __shared__ float s_alpha[64];
+    crf_llh_body(a, s_T, s_alpha);
 }
 
 // ------------------------------------------------------------------------------------------------------ gradient
@@ -176,6 +180,57 @@ __global__ __launch_bounds__(64) void crf_grad_kernel(const CrfArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------- Viterbi
+// forward pass: back-pointers into s_bp, final scores (+ end) into s_alpha; returns the number of decoded positions - as
+// counted here (step 0 always, then the raw mask)
+__device__ __forceinline__ int crf_viterbi_lds(const CrfArgs& a, float* s_T, float* s_alpha, unsigned char* s_bp) {
+    const int b = blockIdx.x, j = threadIdx.x, C = a.C, S = a.S;
+    for (int i = j; i < C * C; i += 64) s_T[i] = a.trans[i];
+    const float* eb = a.e + (int64_t)b * S * a.ld_s;
+    float score = j < C ? a.start[j] + eb[j] : -INFINITY;
+    int len = 1;
+    for (int t = 1; t < S; ++t) {
+        const bool act = on(a, b, t);
+        len += (a.mask == nullptr || a.mask[(int64_t)b * S + t] != 0) ? 1 : 0;
+        __syncthreads();   // block = one wave: orders the LDS exchange
+        if (j < C) s_alpha[j] = score;
+        __syncthreads();   // block = one wave: orders the LDS exchange
+        if (j < C) {
+            int arg = 0;
+            const float nx = reduce_from<true>(s_alpha, s_T, C, j, &arg) + eb[(int64_t)t * a.ld_s + j];
+            s_bp[t * C + j] = (unsigned char)arg;   // history is recorded for every step (as the package does)
+            if (act) score = nx;
+        }
+    }
+    __syncthreads();   // block = one wave: orders the LDS exchange
+    if (j < C) s_alpha[j] = score + a.end[j];
+    __syncthreads();   // block = one wave: orders the LDS exchange
+    return len;
+}
+
+// backtrace (one lane): best final tag from s_fin, then the back-pointers; out[0 .. max(len, 1) - 1] is the path and, with
+// PAD, out[max(len, 1) .. S - 1] = -1
+template <bool PAD, typename T>
+__device__ __forceinline__ void crf_backtrace(const CrfArgs& a, const float* s_fin, const unsigned char* s_bp, int len,
+                                              T* base, int64_t off, float* best_score) {
+    const int C = a.C, S = a.S;
+    int bt = 0;
+    float bs = s_fin[0];
+    for (int i = 1; i < C; ++i)
+        if (s_fin[i] > bs) { bs = s_fin[i]; bt = i; }
+    if (best_score) best_score[blockIdx.x] = bs;
+    T* out = base + off;
+    const int last = len > 0 ? len - 1 : 0;
+    if (PAD)
+        for (int t = last + 1; t < S; ++t) out[t] = -1;
+    out[last] = bt;
+    for (int t = last; t >= 1; --t) {   // history[:seq_end] reversed
+        bt = s_bp[t * C + bt];
+        out[t - 1] = bt;
+    }
+}
+
+// (the decode kernel keeps its own copy of the two helpers above: built from them it compiles to 2 fewer VGPRs, and its
+// code is left as it was; crf_score_decode_kernel uses the helpers)
 __global__ __launch_bounds__(64) void crf_decode_kernel(const CrfArgs a) {
     __shared__ float s_T[64 * 64];
     __shared__ float s_alpha[64];
@@ -259,7 +314,9 @@ __device__ __forceinline__ float lse_shfl(float x, const float (&col)[CM]) {
 
 // log-domain recursions (every step: 16 shuffles + 16 exp + log on the dependent chain): the fallback of the scaled
 // linear-domain kernels below for parameters / emissions whose spread underflows f32
-__device__ __noinline__ void crf_llh_small_log(const CrfArgs& a, const MaskBits& mb) {
+// (ON: MaskBits, or LdsSteps for the score-and-decode kernel, which keeps this body inline and out of scratch)
+template <class ON>
+__device__ __forceinline__ void crf_llh_small_log_body(const CrfArgs& a, const ON& mb) {
     const int b = blockIdx.x, j = threadIdx.x, C = a.C, S = a.S;
     float Tc[CM];
 #pragma unroll
@@ -281,6 +338,7 @@ __device__ __noinline__ void crf_llh_small_log(const CrfArgs& a, const MaskBits&
     const float z = m + __logf(wave_sum(act_lane ? __expf(v - m) : 0.f));
     if (j == 0) a.llh[b] = num - z;
 }
+__device__ __noinline__ void crf_llh_small_log(const CrfArgs& a, const MaskBits& mb) { crf_llh_small_log_body(a, mb); }
 
 __device__ __noinline__ void crf_grad_small_log(const CrfArgs& a, const MaskBits& mb, int len, float* s_al) {
     const int b = blockIdx.x, j = threadIdx.x, C = a.C, S = a.S;
@@ -484,9 +542,8 @@ __device__ __forceinline__ float crf_load_E(const CrfArgs& a, int j, float (&Ec)
     return m;
 }
 
-__global__ __launch_bounds__(64) void crf_llh_small_kernel(const CrfArgs a) {
-    __shared__ float s_x[CRF_LIN_SC];
-    __shared__ unsigned char s_on[64 * MAXW];
+// the scaled form of the log-likelihood; false (nothing written) when the sample needs the log-domain body
+__device__ __forceinline__ bool crf_llh_small_lin(const CrfArgs& a, float* s_x, unsigned char* s_on) {
     const int b = blockIdx.x, j = threadIdx.x;
     if (a.S * a.C <= CRF_LIN_SC) {
         float Ec[CM], Er[CM];
@@ -496,9 +553,17 @@ __global__ __launch_bounds__(64) void crf_llh_small_kernel(const CrfArgs a) {
         if (crf_forward_lin(a, Ec, lzs, s_x, s_on, nullptr, nullptr, f)) {
             const float num = gold_score(a, b, j);
             if (j == 0) a.llh[b] = num - f.logz;
-            return;
+            return true;
         }
     }
+    return false;
+}
+
+__global__ __launch_bounds__(64) void crf_llh_small_kernel(const CrfArgs a) {
+    __shared__ float s_x[CRF_LIN_SC];
+    __shared__ unsigned char s_on[64 * MAXW];
+    const int b = blockIdx.x, j = threadIdx.x;
+    if (crf_llh_small_lin(a, s_x, s_on)) return;
     int len;
     const MaskBits mb = load_mask(a, b, j, &len);
     crf_llh_small_log(a, mb);
@@ -593,11 +658,10 @@ __global__ __launch_bounds__(64) void crf_grad_small_kernel(const CrfArgs a) {
     crf_grad_small_log(a, mb, len, s_buf);
 }
 
-__global__ __launch_bounds__(64) void crf_decode_small_kernel(const CrfArgs a) {
-    __shared__ unsigned char s_bp[CRF_MAX_SC];
-    __shared__ float s_e[CRF_LIN_SC];
-    __shared__ unsigned char s_on[64 * MAXW];
-    __shared__ float s_fin[64];
+// forward pass of the register / shuffle Viterbi: back-pointers into s_bp, final scores (+ end) into s_fin; returns
+// sum(mask) (raw, step 0 included)
+__device__ __forceinline__ int crf_viterbi_small(const CrfArgs& a, unsigned char* s_bp, float* s_e, unsigned char* s_on,
+                                                 float* s_fin) {
     const int b = blockIdx.x, j = threadIdx.x, C = a.C, S = a.S;
     const bool act_lane = j < C;
     float Tc[CM];
@@ -645,21 +709,93 @@ __global__ __launch_bounds__(64) void crf_decode_small_kernel(const CrfArgs a) {
     }
     s_fin[j] = act_lane ? score + a.end[j] : -INFINITY;
     __syncthreads();
-    if (j == 0) {
-        int bt = 0;
-        float bs = s_fin[0];
-        for (int i = 1; i < C; ++i)
-            if (s_fin[i] > bs) { bs = s_fin[i]; bt = i; }
-        if (a.best_score) a.best_score[b] = bs;
-        int64_t* out = a.best + (int64_t)b * S;
-        const int last = len > 0 ? len - 1 : 0;
-        for (int t = last + 1; t < S; ++t) out[t] = -1;
-        out[last] = bt;
-        for (int t = last; t >= 1; --t) {
-            bt = s_bp[t * C + bt];
-            out[t - 1] = bt;
+    return len;
+}
+
+__global__ __launch_bounds__(64) void crf_decode_small_kernel(const CrfArgs a) {
+    __shared__ unsigned char s_bp[CRF_MAX_SC];
+    __shared__ float s_e[CRF_LIN_SC];
+    __shared__ unsigned char s_on[64 * MAXW];
+    __shared__ float s_fin[64];
+    const int len = crf_viterbi_small(a, s_bp, s_e, s_on, s_fin);
+    if (threadIdx.x == 0) crf_backtrace<true>(a, s_fin, s_bp, len, a.best, (int64_t)blockIdx.x * a.S, a.best_score);
+}
+
+// ============================================================================================================
+// Score and decode in one launch (icka_crf_score_decode): optionally the gold-path log-likelihood (the llh kernels' own
+// bodies, so the same bits), then the Viterbi path written WITHOUT padding into tags_flat at this sample's exclusive prefix
+// of the path lengths.  Each wave computes that prefix itself from the mask rows before its own (one ballot per 64
+// positions): no cross-block hand-off, B * b * S mask reads in all, a few microseconds at the B <= 2048 the entry accepts.
+constexpr int CRF_FLAT_MAX_B = 2048;
+
+struct CrfFlatArgs {
+    CrfArgs a;
+    int32_t* lens;   // [B]: path length of each sample
+    int32_t* flat;   // paths back to back, sample b at sum(lens[0 .. b-1])
+};
+
+// step flags in LDS for the log-domain likelihood body (MaskBits index their words dynamically: scratch)
+struct LdsSteps {
+    const unsigned char* s;
+    __device__ __forceinline__ bool on(int t) const { return s[t] != 0; }
+};
+
+// sum over the samples r < b of the path length the decode kernel writes for r: max(positions counted, 1), where a position
+// counts when mask[r][t] != 0 or (FIRST_ON) t == 0  (wave-uniform)
+template <bool FIRST_ON>
+__device__ __forceinline__ int64_t crf_flat_offset(const CrfArgs& a, int b, int lane) {
+    if (a.mask == nullptr) return (int64_t)b * a.S;
+    int64_t off = 0;
+    for (int r = 0; r < b; ++r) {
+        const int64_t* mr = a.mask + (int64_t)r * a.S;
+        int n = 0;
+        for (int t0 = 0; t0 < a.S; t0 += 64) {
+            const int t = t0 + lane;
+            n += __popcll(__ballot(t < a.S && ((FIRST_ON && t == 0) || mr[t] != 0)));
         }
+        off += n > 0 ? n : 1;
     }
+    return off;
+}
+
+template <bool FIRST_ON>
+__device__ __forceinline__ void crf_write_flat(const CrfFlatArgs& d, const float* s_fin, const unsigned char* s_bp, int len) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int64_t off = crf_flat_offset<FIRST_ON>(d.a, b, lane);
+    if (lane == 0) {
+        d.lens[b] = len > 0 ? len : 1;
+        crf_backtrace<false>(d.a, s_fin, s_bp, len, d.flat, off, nullptr);
+    }
+}
+
+__global__ __launch_bounds__(64) void crf_score_decode_kernel(const CrfFlatArgs d) {
+    __shared__ float s_T[64 * 64];
+    __shared__ float s_alpha[64];
+    __shared__ unsigned char s_bp[CRF_MAX_SC];
+    if (d.a.tags) {
+        crf_llh_body(d.a, s_T, s_alpha);
+        __syncthreads();
+    }
+    const int len = crf_viterbi_lds(d.a, s_T, s_alpha, s_bp);
+    crf_write_flat<true>(d, s_alpha, s_bp, len);
+}
+
+__global__ __launch_bounds__(64) void crf_score_decode_small_kernel(const CrfFlatArgs d) {
+    __shared__ unsigned char s_bp[CRF_MAX_SC];
+    __shared__ float s_e[CRF_LIN_SC];   // the likelihood's x_t, then the decode's emissions
+    __shared__ unsigned char s_on[64 * MAXW];
+    __shared__ float s_fin[64];
+    const CrfArgs& a = d.a;
+    if (a.tags && !crf_llh_small_lin(a, s_e, s_on)) {
+        __syncthreads();
+        for (int t = threadIdx.x; t < a.S; t += 64)
+            s_on[t] = (t == 0 || a.mask == nullptr || a.mask[(int64_t)blockIdx.x * a.S + t] != 0) ? 1 : 0;
+        __syncthreads();
+        crf_llh_small_log_body(a, LdsSteps{s_on});
+    }
+    __syncthreads();
+    const int len = crf_viterbi_small(a, s_bp, s_e, s_on, s_fin);
+    crf_write_flat<false>(d, s_fin, s_bp, len);
 }
 
 inline bool crf_small(int S, int C) { return C <= CM && S <= 64 * MAXW; }
@@ -714,6 +850,23 @@ extern "C" int icka_crf_decode(const float* emissions, int64_t ld, const int64_t
     a.best = best_tags; a.best_score = best_score; a.B = B; a.S = S; a.C = C;
     if (crf_small(S, C)) hipLaunchKernelGGL(crf_decode_small_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(crf_decode_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int icka_crf_score_decode(const float* emissions, int64_t ld, const int64_t* tags, const int64_t* mask,
+                                     const float* start, const float* end, const float* trans, float* llh,
+                                     int32_t* lens, int32_t* tags_flat, int64_t capacity, int32_t B, int32_t S,
+                                     int32_t C, void* stream) {
+    if (int rc = crf_check(emissions, start, end, trans, B, S, C)) return rc;
+    if (!lens || !tags_flat || ld < C || (tags == nullptr) != (llh == nullptr)) return ICKA_E_ARG;
+    if ((int64_t)S * C > CRF_MAX_SC || B > CRF_FLAT_MAX_B || capacity < (int64_t)B * S) return ICKA_E_SHAPE;
+    CrfFlatArgs d{};
+    d.a.e = emissions; d.a.ld_s = ld; d.a.tags = tags; d.a.mask = mask; d.a.start = start; d.a.end = end;
+    d.a.trans = trans; d.a.llh = llh; d.a.B = B; d.a.S = S; d.a.C = C;
+    d.lens = lens; d.flat = tags_flat;
+    if (crf_small(S, C)) hipLaunchKernelGGL(crf_score_decode_small_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, d);
+    else hipLaunchKernelGGL(crf_score_decode_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, d);
     ICKA_CHECK_LAUNCH();
     return 0;
 }

@@ -61,6 +61,7 @@ from typing import Callable, Optional
 
 import torch
 
+from . import crf
 from . import kernels as K
 from . import packing
 
@@ -78,6 +79,28 @@ def _sig(values) -> tuple:
             except TypeError:
                 out.append(("const", repr(v)))
     return tuple(out)
+
+
+def _split_output(out, decode: bool):
+    """(DeviceTags | None, tensor | None) of what a captured call returned: ONE floating-point tensor and -- with
+    ``GraphedModule(decode=True)`` -- a ``crf.DeviceTags`` or a ``(DeviceTags, floating-point tensor)`` pair (the dev pass).
+    Anything else raises TypeError (the call then runs eagerly)."""
+    if isinstance(out, torch.Tensor) and out.is_floating_point():
+        return None, out
+    if decode:
+        from .crf import DeviceTags
+        if isinstance(out, DeviceTags):
+            return out, None
+        if (isinstance(out, tuple) and len(out) == 2 and isinstance(out[0], DeviceTags)
+                and isinstance(out[1], torch.Tensor) and out[1].is_floating_point()):
+            if out[1].requires_grad:
+                raise TypeError("GraphedModule(decode=True) captures decoding calls without autograd: this one's loss "
+                                "requires grad")
+            return out
+        raise TypeError("GraphedModule(decode=True) captures calls that return ONE floating-point tensor, a DeviceTags or "
+                        "(DeviceTags, floating-point tensor), got %s" % type(out).__name__)
+    raise TypeError("GraphedModule captures calls that return ONE floating-point tensor (loss or logits), got %s"
+                    % type(out).__name__)
 
 
 def _test_fail(form: str) -> None:
@@ -628,10 +651,14 @@ class _ModuleCapture(_StepBase):
         self._order = {}                        # exchanging captures: the order their bucket flags rise in
         self._grad_slots = []
         model = module
+        decode = owner.decode
+        self._tags = None                       # decode=True: the DeviceTags the captured call writes
 
         def fwd():
             st = self.inputs.static
-            return model(*st[:self._nargs], **dict(zip(self._kwkeys, st[self._nargs:])))
+            # decode=True: the CRF call sites decode into device memory (no host sync) while the call is captured / warmed up
+            with crf.device_decode() if decode else contextlib.nullcontext():
+                return model(*st[:self._nargs], **dict(zip(self._kwkeys, st[self._nargs:])))
 
         self._fwd = fwd
         self.side.wait_stream(torch.cuda.current_stream())
@@ -639,11 +666,8 @@ class _ModuleCapture(_StepBase):
             for _ in range(max(1, warmup)):
                 model.zero_grad()
                 K.bump_dropout_nonce(self.nonce)
-                out = fwd()
-                if not (isinstance(out, torch.Tensor) and out.is_floating_point()):
-                    raise TypeError("GraphedModule captures calls that return ONE floating-point tensor (loss or logits), got %s"
-                                    % type(out).__name__)
-                if out.requires_grad:
+                _, out = _split_output(fwd(), decode)
+                if out is not None and out.requires_grad:
                     out.backward(torch.ones_like(out))
                     if reducer is not None:
                         reducer.finish()       # (eager exchange: the first of these steps calibrates its write counts)
@@ -665,10 +689,10 @@ class _ModuleCapture(_StepBase):
             self.gf = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.gf, capture_error_mode="thread_local"):
                 K.bump_dropout_nonce(self.nonce)
-                self.out = fwd()
+                self._tags, self.out = _split_output(fwd(), decode)
                 _test_fail("module")
-            self.gout = torch.zeros_like(self.out)
-            if self.out.requires_grad:
+            self.gout = torch.zeros_like(self.out) if self.out is not None else None
+            if self.out is not None and self.out.requires_grad:
                 # every capture a backward() can ask for is taken NOW: a capture runs autograd itself and must not start from
                 # inside the autograd call that replays it
                 k = self.accumulate
@@ -748,6 +772,13 @@ class _ModuleCapture(_StepBase):
 
     def run(self, values) -> torch.Tensor:
         self._prepare(self.gf is None, values, flags=self.reducer is not None)
+        if self._tags is not None:              # decode=True: what the eager model returns -- lists, or (lists, loss)
+            self.gf.replay()
+            tags = self._tags.tolist()          # (the one host sync of the call)
+            # after that sync an error word of THIS replay is already set: raise it here, not with the next call
+            K.lstm_check_error(self._detected)
+            K.gemm_ln_check_error(self._detected)
+            return tags if self.out is None else (tags, self.out.detach())
         if torch.is_grad_enabled() and self._bwd:
             return self._fn.apply(self.arena.anchor)
         self.gf.replay()
@@ -794,10 +825,18 @@ class GraphedModule(object):
     restarts at ``zero_grad``) exchanges, the others replay captures without the reducer; eager calls follow the same count.
     Whether a grad-mode call signature is replayed or run eagerly is agreed ACROSS the ranks (module docstring: warm-up =
     collective phase, capture = local phase, then a vote over the store); a disagreement on the example call raises
-    ``dp.CaptureDisagreement`` on every rank, on a later signature all ranks run it eagerly."""
+    ``dp.CaptureDisagreement`` on every rank, on a later signature all ranks run it eagerly.
+
+    Decoding (``decode=True``, opt-in): the CRF models' dev and test calls (``mode="dev"`` -> ``(pred_tags, loss)``,
+    ``mode="test"`` / ``use_crf=True`` without labels -> ``pred_tags``) return python lists and sync the host inside the forward,
+    so by default they run eagerly.  With ``decode=True`` the wrapper runs the module under ``crf.device_decode()``, where those
+    call sites decode with ``icka_crf_score_decode`` into a ``crf.DeviceTags`` (the dev loss from the same launch); such calls are
+    captured and replayed like any other, under the same cache key, and each replay returns the lists (``tolist()``: one
+    device-to-host copy) or ``(lists, loss)`` -- the types the eager model returns (the loss is the static output, as above).
+    Calls past ``max_captures``, or whose capture fails, still run eagerly and return the eager model's lists."""
 
     def __init__(self, module: torch.nn.Module, example_args=(), example_kwargs=None, warmup: int = 3, reducer=None,
-                 accumulate: int = 1, max_captures: int = 4):
+                 accumulate: int = 1, max_captures: int = 4, decode: bool = False):
         if accumulate < 1:
             raise ValueError("accumulate must be >= 1")
         if max_captures < 1:
@@ -815,6 +854,7 @@ class GraphedModule(object):
         d["reducer"] = reducer
         d["accumulate"] = int(accumulate)
         d["max_captures"] = int(max_captures)
+        d["decode"] = bool(decode)
         d["_warmup"] = warmup
         d["_cycle"] = _Cycle(int(accumulate)) if reducer is not None else None
         d["_caps"] = {}

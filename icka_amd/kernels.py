@@ -926,6 +926,42 @@ def crf_decode(emissions, mask, start, end, trans, best_tags, best_score=None):
     return best_tags
 
 
+CRF_FLAT_MAX_B = 2048   # icka_crf_score_decode: the batch size up to which the kernel computes the path offsets itself
+
+
+def crf_score_decode(emissions, tags, mask, start, end, trans, llh, lens, tags_flat):
+    """Viterbi paths of all samples into ``tags_flat`` (int32, back to back) with their lengths in ``lens`` (int32 [B]) and,
+    when ``tags`` is given, the gold-path log-likelihood into ``llh`` (f32 [B]) -- one launch, no host sync."""
+    B, S, Cn = _crf_check(emissions, start, end, trans)
+    _i64(tags, "tags", (B, S)); _i64(mask, "mask", (B, S))
+    check_flat_tags(lens, tags_flat, B, S)
+    if (tags is None) != (llh is None):
+        raise ValueError("crf_score_decode: tags and llh go together")
+    if llh is not None:
+        _dev(llh, "llh")
+        if llh.dtype != F32 or tuple(llh.shape) != (B,) or not llh.is_contiguous():
+            raise ValueError("llh must be contiguous f32 [%d]" % B)
+    _dev(lens, "lens"); _dev(tags_flat, "tags_flat")
+    if B > CRF_FLAT_MAX_B:
+        raise ValueError("crf_score_decode: B = %d > %d" % (B, CRF_FLAT_MAX_B))
+    check(_lib.load().icka_crf_score_decode(emissions.data_ptr(), Cn, _ptr(tags), _ptr(mask), start.data_ptr(),
+                                            end.data_ptr(), trans.data_ptr(), _ptr(llh), lens.data_ptr(),
+                                            tags_flat.data_ptr(), tags_flat.numel(), B, S, Cn, _stream()),
+          "icka_crf_score_decode")
+
+
+def check_flat_tags(lens, tags_flat, B, S):
+    """Host-side checks of the outputs of crf_score_decode (no device access): int32, 1-D, contiguous, ``lens`` [B] and room
+    for B * S tags."""
+    for n, t in (("lens", lens), ("tags_flat", tags_flat)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous 1-D int32 tensor, got %s %s" % (n, t.dtype, tuple(t.shape)))
+    if lens.numel() != B:
+        raise ValueError("lens holds %d entries for a batch of %d" % (lens.numel(), B))
+    if tags_flat.numel() < B * S:
+        raise ValueError("tags_flat holds %d tags, a batch of %d x %d needs up to %d" % (tags_flat.numel(), B, S, B * S))
+
+
 # ------------------------------------------------------------------------------------------------- helpers
 def cast_f32_to_bf16(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     _dev(src, "src"); _dev(dst, "dst")

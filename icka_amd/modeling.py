@@ -1035,8 +1035,9 @@ class MTCCMBertForMMTokenClassificationCRF_gate_1(BertPreTrainedModel):
         if mode == "train":
             return -self.crf(emissions, tags=labels, mask=output_mask, reduction="token_mean")
         if mode == "dev":
-            pred_tags = self.crf.decode(emissions, mask=output_mask)
-            return pred_tags, -self.crf(emissions, tags=labels, mask=output_mask, reduction="token_mean")
+            # = (crf.decode(...), crf(..., reduction="token_mean")); one launch under crf.device_decode()
+            pred_tags, llh = self.crf.decode_llh(emissions, labels, mask=output_mask, reduction="token_mean")
+            return pred_tags, -llh
         if mode == "test":
             return self.crf.decode(emissions, mask=output_mask)
         return emissions

@@ -518,6 +518,15 @@ int icka_crf_grad(const float* emissions, int64_t ld, const int64_t* tags, const
 int icka_crf_decode(const float* emissions, int64_t ld, const int64_t* mask, const float* start, const float* end,
                     const float* trans, int64_t* best_tags, float* best_score, int32_t B, int32_t S, int32_t C,
                     void* stream);
+/* Score and decode in one launch, with no host sync (graph-capturable decoding).  lens int32 [B]: the length of each
+ * sample's Viterbi path (the entries icka_crf_decode writes before its -1 filler: sum(mask[b]), at least 1).
+ * tags_flat int32 [capacity >= B*S]: the paths of all samples back to back, sample b at sum(lens[0 .. b-1]) (the kernel
+ * computes the offset itself; entries past sum(lens) are left as they are).  Tags equal icka_crf_decode's.  tags and llh
+ * are both NULL or both set: llh f32 [B] is then the gold-path log-likelihood, bit for bit icka_crf_llh's.
+ * S*C <= 12288, B <= 2048. */
+int icka_crf_score_decode(const float* emissions, int64_t ld, const int64_t* tags, const int64_t* mask,
+                          const float* start, const float* end, const float* trans, float* llh, int32_t* lens,
+                          int32_t* tags_flat, int64_t capacity, int32_t B, int32_t S, int32_t C, void* stream);
 /* ---------------------------------------------------------------------------------------------------------------
  * Bidirectional single-layer LSTM of the tagging tail:
  * nn.LSTM(H, H, batch_first=True, bidirectional=True) at Cross_Modal_Interaction_Module.py:905-908, called :1042
