@@ -8,6 +8,10 @@
 //   maxpool3x3s2 : nn.MaxPool2d(3, 2, 1)
 //   features_out : last NHWC map -> att f32 [B,C,7,7] (F.adaptive_avg_pool2d(x,[7,7]) of a 7x7 map = identity),
 //                  fc = mean over the 49 positions, and the region-token matrix bf16 [B*49, C] the MNER trunk reads.
+// Train-mode BatchNorm (ResNet.train_batchnorm) replaces the fold by three steps per BatchNorm: the convolution GEMM writes
+// the raw output and per-tile partial statistics (gemm.hip, icka_gemm_bn_stats / icka_conv3x3_gemm_stats), then
+//   bn_finalize  : partials -> batch mean / variance -> scale, shift + the running-statistics update, on the device
+//   bn_apply     : relu(raw * scale + shift [+ residual]), the residual optionally through the downsample's scale / shift
 // Rows past the last valid row of a padded (multiple-of-128) GEMM operand are written as zeros.
 #include "common.h"
 
@@ -121,6 +125,94 @@ __global__ void features_out_kernel(const bf16_t* __restrict__ x, float* __restr
     }
 }
 
+// Train-mode BatchNorm, per channel c: merge the [tiles] partials of icka_gemm_bn_stats / icka_conv3x3_gemm_stats in a fixed
+// order (thread (c, j) takes tiles j, j+16, ... in turn, then the 16 slices are merged in slice order), so an eager call and a
+// graph replay give the same bits.  Block = 16 channels x 16 slices.
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ part, int tiles, int C, const float* __restrict__ weight,
+                                                          const float* __restrict__ bias, float* __restrict__ running_mean,
+                                                          float* __restrict__ running_var, const int64_t* __restrict__ nbt, float momentum,
+                                                          float eps, float* __restrict__ scale, float* __restrict__ shift) {
+    __shared__ float red[3][256];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int c = blockIdx.x * 16 + tx;
+    const int64_t plane = (int64_t)tiles * C;
+    float n = 0.f, mu = 0.f, m2 = 0.f;
+    if (c < C)
+        for (int t = ty; t < tiles; t += 16) {
+            const int64_t at = (int64_t)t * C + c;
+            bn_chan_merge(n, mu, m2, part[at], part[plane + at], part[2 * plane + at]);
+        }
+    red[0][threadIdx.x] = n;
+    red[1][threadIdx.x] = mu;
+    red[2][threadIdx.x] = m2;
+    __syncthreads();
+    if (ty != 0 || c >= C) return;
+    for (int j = 1; j < 16; ++j) bn_chan_merge(n, mu, m2, red[0][j * 16 + tx], red[1][j * 16 + tx], red[2][j * 16 + tx]);
+    const float var = n > 0.f ? m2 / n : 0.f;                 // biased: the normalisation
+    const float sc = weight[c] * (1.f / sqrtf(var + eps));
+    scale[c] = sc;
+    shift[c] = bias[c] - mu * sc;
+    // momentum < 0: cumulative average, 1 / num_batches_tracked after this call's increment (icka_bn_apply adds the 1)
+    const float m = momentum >= 0.f ? momentum : 1.f / (float)(nbt[0] + 1);
+    const float unbiased = n > 1.f ? var * (n / (n - 1.f)) : var;
+    running_mean[c] = m * mu + (1.f - m) * running_mean[c];
+    running_var[c] = m * unbiased + (1.f - m) * running_var[c];
+}
+
+__device__ __forceinline__ void load8_f32(const float* p, float (&o)[8]) {   // p 32-byte aligned
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { o[e] = a[e]; o[4 + e] = b[e]; }
+}
+
+// y = [relu](raw * scale + shift [+ residual]) on rows < rows_valid, zeros on [rows_valid, rows_padded).  residual: bf16 as is, or
+// (res_scale) residual * res_scale + res_shift (the downsample branch's BatchNorm).  raw / y / residual: [rows_padded, C], y may be
+// raw.  The first thread also adds 1 to the num_batches_tracked counters of the BatchNorms it applies.
+__global__ void bn_apply_kernel(const bf16_t* raw, const float* __restrict__ scale, const float* __restrict__ shift, const bf16_t* res,
+                                const float* __restrict__ res_scale, const float* __restrict__ res_shift, bf16_t* y, int C,
+                                int64_t rows_valid, int64_t rows_padded, int relu, int64_t* nbt_a, int64_t* nbt_b) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (nbt_a) nbt_a[0] = nbt_a[0] + 1;
+        if (nbt_b) nbt_b[0] = nbt_b[0] + 1;
+    }
+    const int cpr = C >> 3;
+    const int64_t total = rows_padded * cpr;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = i / cpr;
+        const int c0 = (int)(i - row * cpr) * 8;
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = f2bf(0.f);
+        if (row < rows_valid) {
+            const bf16x8 v = as_bf16x8(*reinterpret_cast<const u32x4*>(raw + row * C + c0));
+            float r[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) r[e] = 0.f;
+            float sc[8], sh[8];
+            load8_f32(scale + c0, sc);
+            load8_f32(shift + c0, sh);
+            if (res) {
+                const bf16x8 rv = as_bf16x8(*reinterpret_cast<const u32x4*>(res + row * C + c0));
+#pragma unroll
+                for (int e = 0; e < 8; ++e) r[e] = bf2f(rv[e]);
+                if (res_scale) {
+                    float rs[8], rb[8];
+                    load8_f32(res_scale + c0, rs);
+                    load8_f32(res_shift + c0, rb);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) r[e] = r[e] * rs[e] + rb[e];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float t = bf2f(v[e]) * sc[e] + sh[e] + r[e];
+                o[e] = f2bf(relu ? fmaxf(t, 0.f) : t);
+            }
+        }
+        *reinterpret_cast<u32x4*>(y + row * C + c0) = as_u32x4(o);
+    }
+}
+
 inline int grid_for(int64_t n) {
     int64_t g = (n + 255) / 256;
     return (int)(g > 65536 ? 65536 : (g < 1 ? 1 : g));
@@ -171,6 +263,32 @@ extern "C" int icka_conv_maxpool3x3s2(const void* src, void* dst, int32_t B, int
     if (rows_padded < (int64_t)B * Ho * Wo) return ICKA_E_SHAPE;
     hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid_for(rows_padded * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)src, (bf16_t*)dst, B, H, W, C, Ho, Wo, rows_padded);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int icka_bn_finalize(const float* partials, int32_t tiles, int32_t C, const float* weight, const float* bias,
+                                float* running_mean, float* running_var, const int64_t* num_batches_tracked, float momentum, float eps,
+                                float* scale, float* shift, void* stream) {
+    if (!partials || !weight || !bias || !running_mean || !running_var || !num_batches_tracked || !scale || !shift) return ICKA_E_ARG;
+    if (tiles <= 0 || C <= 0 || !(eps >= 0.f)) return ICKA_E_SHAPE;
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, (hipStream_t)stream, partials, tiles, C, weight, bias,
+                       running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int icka_bn_apply(const void* raw, const float* scale, const float* shift, const void* residual, const float* res_scale,
+                             const float* res_shift, void* y, int32_t C, int64_t rows_valid, int64_t rows_padded, int32_t relu,
+                             int64_t* nbt_a, int64_t* nbt_b, void* stream) {
+    if (!raw || !scale || !shift || !y || (res_scale && (!residual || !res_shift))) return ICKA_E_ARG;
+    if (C <= 0 || C % 8 || rows_valid < 0 || rows_padded < rows_valid) return ICKA_E_SHAPE;
+    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (!al(raw) || !al(y) || (residual && !al(residual)) || !al(scale) || !al(shift) || (res_scale && (!al(res_scale) || !al(res_shift))))
+        return ICKA_E_ALIGN;
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(rows_padded * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)raw,
+                       scale, shift, (const bf16_t*)residual, res_scale, res_shift, (bf16_t*)y, C, rows_valid, rows_padded, relu,
+                       nbt_a, nbt_b);
     ICKA_CHECK_LAUNCH();
     return 0;
 }

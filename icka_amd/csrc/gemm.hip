@@ -856,6 +856,46 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, char* smem, con
     epilogue_rows<16, 16, 0, A_KM>(g, smem, m0, n0, tid);
 }
 
+// Train-mode BatchNorm partials of one staged f32 output tile (off_c image at smem_c): per tile column n, (count, mean, M2)
+// over the tile's rows m < rows_valid, written to part[k * (M / 128) * N + (m0 / 128) * N + n] for k = count, mean, M2.
+// Thread (c, q) takes column c over the q-th 128 / NQ-row slice (two passes over LDS: mean, then squared deviations; q is
+// wave-uniform); the q == 0 threads merge the NQ slices in slice order, so every partial is a fixed function of the tile.
+// smem_red: 6 KiB of LDS past the C tile for the slices.
+template <int BNT>
+__device__ __forceinline__ void bn_stats_tile(const char* smem_c, char* smem_red, int m0, int n0, int tid, int M, int N, float* part,
+                                              int rows_valid) {
+    constexpr int NQ = 512 / BNT, RQ = 128 / NQ;
+    const int c = tid % BNT, q = tid / BNT;
+    int nv = rows_valid - m0;
+    nv = nv < 0 ? 0 : (nv > BM ? BM : nv);
+    const int r0 = q * RQ;
+    const int r1 = r0 + RQ < nv ? r0 + RQ : nv;
+    const int cnt = r1 > r0 ? r1 - r0 : 0;
+    const char* col = smem_c + 4 * (c & 3);
+    float s = 0.f;
+    for (int r = r0; r < r1; ++r) s += *reinterpret_cast<const float*>(col + off_c(r, c >> 2));
+    const float mean = cnt ? s / (float)cnt : 0.f;
+    float m2 = 0.f;
+    for (int r = r0; r < r1; ++r) {
+        const float d = *reinterpret_cast<const float*>(col + off_c(r, c >> 2)) - mean;
+        m2 += d * d;
+    }
+    float* red = reinterpret_cast<float*>(smem_red);
+    red[tid] = (float)cnt;
+    red[512 + tid] = mean;
+    red[1024 + tid] = m2;
+    __syncthreads();
+    if (q == 0) {
+        float n = 0.f, mu = 0.f, M2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) bn_chan_merge(n, mu, M2, red[j * BNT + c], red[512 + j * BNT + c], red[1024 + j * BNT + c]);
+        const int64_t plane = (int64_t)(M / BM) * N, at = (int64_t)(m0 / BM) * N + n0 + c;
+        part[at] = n;
+        part[plane + at] = mu;
+        part[2 * plane + at] = M2;
+    }
+}
+
 __device__ __forceinline__ bool g_direct_epilogue(const GemmArgs& g) {
     // f32 outputs only: 16 B per lane.  bf16 outputs (8 B per lane, 32-byte row pieces) measured 5 % slower than the
     // staged 16-byte row-contiguous stores (qkv projection, profiles/README.md)
@@ -871,8 +911,12 @@ __device__ __forceinline__ bool g_direct_epilogue(const GemmArgs& g) {
 // after finishing tile kt-1, so the barrier both publishes tile kt and frees the buffer of tile kt-1 for re-staging.
 // LNF (gemm_ln_kernel): the tile's plain f32 output is stored WRITE-THROUGH (sc1) and the body returns instead of retiring its
 // waves -- the kernel then hands the stripe's rows over to its LayerNorm phase inside the same launch.
-template <bool A_KM, bool B_KM, int NBUF, int ABL = 0, int DIST = 2, int BNT = 128, bool F16 = false, bool CONV = false, bool LNF = false>
-__device__ __forceinline__ void gemm_ws_body(const GemmArgs& g, char* smem, const int bid, const int nb) {
+// STATS (gemm_ws_bn_stats_kernel): the raw output tile (no bias / activation) is stored as usual, and bn_stats_tile writes
+// the train-mode BatchNorm partials of its columns from the f32 tile in LDS to stats_part.
+template <bool A_KM, bool B_KM, int NBUF, int ABL = 0, int DIST = 2, int BNT = 128, bool F16 = false, bool CONV = false, bool LNF = false,
+          bool STATS = false>
+__device__ __forceinline__ void gemm_ws_body(const GemmArgs& g, char* smem, const int bid, const int nb, float* stats_part = nullptr,
+                                             int stats_rows = 0) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(LDS_PTR(char, smem)));
@@ -1208,6 +1252,10 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& g, char* smem, cons
         }
     }
     __syncthreads();
+    if constexpr (STATS) {
+        static_assert(NBUF * 2 * TILE_BYTES >= 128 * 512 + 3 * 512 * 4, "LDS room for the statistics slices");
+        bn_stats_tile<BNT>(smem, smem + 128 * 512, m0, n0, tid, g.M, g.N, stats_part, stats_rows);
+    }
     epilogue_rows<32, BNT / 8, 0, A_KM>(g, smem, m0, n0, tid);
 #ifdef ICKA_GEMM_STAMP
     if (g.stamp && lane == 0 && wave == 0) {
@@ -1224,6 +1272,16 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const GemmArgs gp) {
     const GemmArgs g = gp;
     __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * TILE_BYTES];
     gemm_ws_body<A_KM, B_KM, NBUF, ABL, 2, BNT, F16, CONV>(g, smem, blockIdx.x, gridDim.x);
+}
+
+// Convolution GEMM of a train-mode BatchNorm layer (icka_gemm_bn_stats, icka_conv3x3_gemm_stats): NT, bf16, 128 x BNT tiles,
+// raw bf16 output + the per-(row tile, column) partials of bn_stats_tile.
+struct BnStatsArgs { GemmArgs g; float* part; int rows_valid; };
+template <int BNT, bool CONV>
+__global__ __launch_bounds__(512) void gemm_ws_bn_stats_kernel(const BnStatsArgs p) {
+    const GemmArgs g = p.g;
+    __shared__ __attribute__((aligned(16))) char smem[3 * 2 * TILE_BYTES];
+    gemm_ws_body<false, false, 3, 0, 2, BNT, false, CONV, false, true>(g, smem, blockIdx.x, gridDim.x, p.part, p.rows_valid);
 }
 
 // =====================================================================================================================
@@ -2109,6 +2167,60 @@ extern "C" int icka_conv3x3_gemm(const void* x, const void* w, const float* bias
         hipLaunchKernelGGL((gemm_ws_kernel<false, false, 3, 0, 128, false, true>), dim3((g.M / BM) * (Cout / 128)), dim3(512), 0, st, g);
     else
         hipLaunchKernelGGL((gemm_ws_kernel<false, false, 3, 0, 64, false, true>), dim3((g.M / BM) * (Cout / 64)), dim3(512), 0, st, g);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+// Train-mode BatchNorm convolutions: the raw output (no bias, no activation) + per-(row tile, channel) partial statistics of
+// the f32 accumulators over the rows m < rows_valid (see icka_hip.h).  128 x 128 tiles where N % 128 == 0, else 128 x 64.
+static int launch_bn_stats(BnStatsArgs& p, hipStream_t st) {
+    GemmArgs& g = p.g;
+    g.K1 = 0; g.alpha = 1.f; g.beta = 0.f; g.epi = ICKA_EPI_NONE; g.c_f32 = 0; g.a_vec = g.b_vec = 1; g.ksplit = 1; g.direct = 0;
+    if (g.N % 128 == 0)
+        hipLaunchKernelGGL((gemm_ws_bn_stats_kernel<128, false>), dim3((g.M / BM) * (g.N / 128)), dim3(512), 0, st, p);
+    else
+        hipLaunchKernelGGL((gemm_ws_bn_stats_kernel<64, false>), dim3((g.M / BM) * (g.N / 64)), dim3(512), 0, st, p);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int icka_gemm_bn_stats(const void* a, int64_t lda, const void* w, int64_t ldw, void* y, int64_t ldy, int32_t M, int32_t N,
+                                  int32_t K, int64_t rows_valid, float* partials, void* stream) {
+    if (!a || !w || !y || !partials) return ICKA_E_ARG;
+    if (M <= 0 || M % BM || N <= 0 || N % 64 || K <= 0 || K % BK || rows_valid < 1 || rows_valid > M) return ICKA_E_SHAPE;
+    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (!al(a) || !al(w) || !al(y) || !al(partials) || lda % 8 || ldw % 8 || ldy % 8 || lda < K || ldw < K || ldy < N)
+        return ICKA_E_ALIGN;
+    BnStatsArgs p{};
+    p.g.M = M; p.g.N = N; p.g.K = K;
+    p.g.A = (const bf16_t*)a; p.g.lda = lda; p.g.B = (const bf16_t*)w; p.g.ldb = ldw; p.g.C = y; p.g.ldc = ldy;
+    p.part = partials; p.rows_valid = (int)rows_valid;
+    return launch_bn_stats(p, (hipStream_t)stream);
+}
+
+extern "C" int icka_conv3x3_gemm_stats(const void* x, const void* w, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Cout,
+                                       int32_t stride, int64_t rows_padded, const void* zeros, float* partials, void* stream) {
+    if (!x || !w || !y || !zeros || !partials) return ICKA_E_ARG;
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 64 || Cout <= 0 || Cout % 64 || (stride != 1 && stride != 2))
+        return ICKA_E_SHAPE;
+    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+    const int64_t rows = (int64_t)B * Ho * Wo;
+    if (rows_padded < rows || rows_padded % BM || rows_padded > 0x7fffffff) return ICKA_E_SHAPE;
+    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (!al(x) || !al(w) || !al(y) || !al(zeros) || !al(partials)) return ICKA_E_ALIGN;
+    BnStatsArgs p{};
+    p.g.M = (int)rows_padded; p.g.N = Cout; p.g.K = 9 * C;
+    p.g.A = (const bf16_t*)x; p.g.lda = C; p.g.B = (const bf16_t*)w; p.g.ldb = 9 * (int64_t)C; p.g.C = y; p.g.ldc = Cout;
+    p.g.cvH = H; p.g.cvW = W; p.g.cvC = C; p.g.cvS = stride; p.g.cvHo = Ho; p.g.cvWo = Wo; p.g.cvRows = (int)rows;
+    p.g.cvZero = (const bf16_t*)zeros;
+    p.part = partials; p.rows_valid = (int)rows;
+    GemmArgs& g = p.g;
+    g.K1 = 0; g.alpha = 1.f; g.beta = 0.f; g.epi = ICKA_EPI_NONE; g.c_f32 = 0; g.a_vec = g.b_vec = 1; g.ksplit = 1; g.direct = 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (Cout % 128 == 0)
+        hipLaunchKernelGGL((gemm_ws_bn_stats_kernel<128, true>), dim3((g.M / BM) * (Cout / 128)), dim3(512), 0, st, p);
+    else
+        hipLaunchKernelGGL((gemm_ws_bn_stats_kernel<64, true>), dim3((g.M / BM) * (Cout / 64)), dim3(512), 0, st, p);
     ICKA_CHECK_LAUNCH();
     return 0;
 }

@@ -1324,3 +1324,74 @@ def sample_swap(x, y, B: int, n_neg: int):
     check(_lib.load().icka_sample_swap(x.data_ptr(), y.data_ptr(), B, x.numel() // B * x.element_size(), int(n_neg), _stream()),
           "icka_sample_swap")
     return y
+
+
+# ---------------------------------------------------------------------------------------------------- train-mode BatchNorm
+def gemm_bn_stats(a: torch.Tensor, w: torch.Tensor, rows_valid: int):
+    """Convolution GEMM of a train-mode BatchNorm layer: raw bf16 [M, N] = a . w^T (a [M, K], w [N, K], NT; no bias, no
+    activation) and the partial statistics f32 [3, M/128, N] = (count, mean, M2) of each 128-row tile and channel over the
+    rows < rows_valid, from the f32 accumulators (icka_gemm_bn_stats)."""
+    _mat(a, "a"); _mat(w, "w")
+    M, K = a.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError("gemm_bn_stats: a [M, K], w [N, K]")
+    raw = torch.empty(M, N, dtype=BF16, device=a.device)
+    part = torch.empty(3, M // 128, N, dtype=F32, device=a.device)
+    check(_lib.load().icka_gemm_bn_stats(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), raw.data_ptr(), N, M, N, K,
+                                         rows_valid, part.data_ptr(), _stream()), "icka_gemm_bn_stats")
+    return raw, part
+
+
+def conv3x3_bn_stats(x: torch.Tensor, w: torch.Tensor, B: int, H: int, W: int, C: int, Cout: int, stride: int, rows_padded: int,
+                     zeros: torch.Tensor):
+    """The implicit 3x3 / pad 1 convolution of icka_conv3x3_gemm (x NHWC bf16 rows, w bf16 [Cout, 9 C]) for a train-mode
+    BatchNorm layer: raw bf16 [rows_padded, Cout] + partials f32 [3, rows_padded/128, Cout] (icka_conv3x3_gemm_stats)."""
+    _dev(x, "x")
+    if x.dtype != BF16 or w.dtype != BF16 or not x.is_contiguous() or not w.is_contiguous():
+        raise ValueError("conv3x3_bn_stats: contiguous bf16 operands")
+    raw = torch.empty(rows_padded, Cout, dtype=BF16, device=x.device)
+    part = torch.empty(3, rows_padded // 128, Cout, dtype=F32, device=x.device)
+    check(_lib.load().icka_conv3x3_gemm_stats(x.data_ptr(), w.data_ptr(), raw.data_ptr(), B, H, W, C, Cout, stride, rows_padded,
+                                              zeros.data_ptr(), part.data_ptr(), _stream()), "icka_conv3x3_gemm_stats")
+    return raw, part
+
+
+def bn_finalize(part: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_mean: torch.Tensor,
+                running_var: torch.Tensor, num_batches_tracked: torch.Tensor, momentum: Optional[float], eps: float):
+    """Batch statistics from the partials of gemm_bn_stats / conv3x3_bn_stats -> (scale, shift) f32 [C], and the running
+    statistics updated in place on the device (icka_bn_finalize).  momentum None = cumulative average."""
+    _dev(part, "partials")
+    _, tiles, Cn = part.shape
+    for t, name in ((weight, "weight"), (bias, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if t.dtype != F32 or t.numel() != Cn or not t.is_contiguous() or t.device != part.device:
+            raise TypeError("bn_finalize: %s must be contiguous f32 [%d] on %s" % (name, Cn, part.device))
+    if num_batches_tracked.dtype != torch.int64 or num_batches_tracked.device != part.device:
+        raise TypeError("bn_finalize: num_batches_tracked must be an int64 device tensor")
+    scale = torch.empty(Cn, dtype=F32, device=part.device)
+    shift = torch.empty(Cn, dtype=F32, device=part.device)
+    check(_lib.load().icka_bn_finalize(part.data_ptr(), tiles, Cn, weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
+                                       running_var.data_ptr(), num_batches_tracked.data_ptr(),
+                                       -1.0 if momentum is None else float(momentum), float(eps), scale.data_ptr(),
+                                       shift.data_ptr(), _stream()), "icka_bn_finalize")
+    return scale, shift
+
+
+def bn_apply(raw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, rows_valid: int, relu: bool = True,
+             residual: Optional[torch.Tensor] = None, res_scale: Optional[torch.Tensor] = None,
+             res_shift: Optional[torch.Tensor] = None, nbt=(), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = [relu](raw * scale + shift [+ residual (* res_scale + res_shift)]) on rows < rows_valid, zeros below; adds 1 to each
+    num_batches_tracked tensor of ``nbt`` (at most two).  out defaults to raw (in place) (icka_bn_apply)."""
+    _mat(raw, "raw")
+    if residual is not None:
+        _mat(residual, "residual")
+        if residual.shape != raw.shape or not residual.is_contiguous():
+            raise ValueError("bn_apply: residual must match raw")
+    if not raw.is_contiguous() or len(nbt) > 2:
+        raise ValueError("bn_apply: contiguous raw, at most two counters")
+    out = raw if out is None else out
+    p = [t.data_ptr() for t in nbt] + [None] * (2 - len(nbt))
+    check(_lib.load().icka_bn_apply(raw.data_ptr(), scale.data_ptr(), shift.data_ptr(), _ptr(residual), _ptr(res_scale),
+                                    _ptr(res_shift), out.data_ptr(), raw.shape[1], rows_valid, raw.shape[0], int(bool(relu)),
+                                    p[0], p[1], _stream()), "icka_bn_apply")
+    return out

@@ -9,8 +9,15 @@ Every convolution is a GEMM of the GEMM kernels on NHWC bf16 activations: eval-m
 (bf16) weights and an f32 bias when the module is first used (re-folded when a parameter changes), ReLU and the
 residual add live in the GEMM epilogue, 3x3 / 7x7 convolutions go through patch matrices built by `icka_conv_*`.
 The row count of every feature map is zero-padded to a multiple of 128 and channel counts to 64 (stem / layer1:
-128x64 GEMM tiles) or multiples of 128, so that all GEMMs take the fast path.  There is no backward: the encoder is frozen in the reference
-run (``fine_tune_cnn`` off) and ``if_fine_tune=True`` raises."""
+128x64 GEMM tiles) or multiples of 128, so that all GEMMs take the fast path.  There is no backward: the encoder's weights
+are frozen in the reference run (``fine_tune_cnn`` off) and ``if_fine_tune=True`` raises.
+
+Its BatchNorm statistics are not: the reference calls ``encoder.train()`` every epoch and runs the encoder under
+``no_grad`` in training mode (My_cross_attention.py:791-805), so every BatchNorm normalises with the batch's statistics and
+moves its running statistics.  ``ResNet(..., train_batchnorm=True)`` (opt-in) does the same in ``.train()``: each BN'd
+convolution runs unfolded as a GEMM that also leaves per-tile partial statistics, a finalise launch (batch mean / variance,
+running-statistics update on the device) and an apply launch (scale, shift, residual, ReLU).  ``.eval()`` keeps the folded
+path, which then reads the running statistics as training left them."""
 from __future__ import annotations
 
 import math
@@ -54,7 +61,7 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, block, layers, num_classes=1000):
+    def __init__(self, block, layers, num_classes=1000, train_batchnorm=False):
         if block is not Bottleneck:
             raise ValueError("icka_amd.resnet implements the Bottleneck networks (resnet50/101/152)")
         self.inplanes = 64
@@ -80,6 +87,15 @@ class ResNet(nn.Module):
         self._folded_key = None
         # 3x3 convolutions as implicit GEMMs (icka_conv3x3_gemm); False = patch matrix (icka_conv_im2col3x3) + GEMM
         self.implicit_conv = True
+        # nn.BatchNorm2d semantics in .train(): batch statistics + running-statistics update (False: .train() raises)
+        self.train_batchnorm = bool(train_batchnorm)
+        self._train_w = None
+        self._train_w_key = None
+        # the kernels write the running statistics without moving their version counters: after an eager train-mode forward
+        # the next eval forward re-folds (_bn_moved); once a train-mode forward was captured into a graph, whose replays can
+        # run at any time, every eval forward re-folds (_bn_graphed)
+        self._bn_moved = False
+        self._bn_graphed = False
         # load_state_dict always invalidates the folded weights (version counters also move, but be explicit)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.refold())
 
@@ -90,6 +106,8 @@ class ResNet(nn.Module):
         call refold() yourself after writing parameters through ``.data`` (invisible to version counters)."""
         self._folded = None
         self._folded_key = None
+        self._train_w = None
+        self._train_w_key = None
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
@@ -111,6 +129,13 @@ class ResNet(nn.Module):
         scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
         bias = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
         w = w * scale[:, None, None, None]
+        b = torch.zeros(cout_pad, dtype=F32, device=w.device)
+        b[:w.shape[0]] = bias
+        return ResNet._gemm_weight(w, cin_pad, cout_pad, k_pad), b.contiguous()
+
+    @staticmethod
+    def _gemm_weight(w: torch.Tensor, cin_pad: int, cout_pad: int, k_pad: int = 0) -> torch.Tensor:
+        """f32 conv weight [cout, cin, kh, kw] -> bf16 GEMM operand [cout_pad, taps*cin_pad (or k_pad)]."""
         cout, cin, kh, kw = w.shape
         w = w.permute(0, 2, 3, 1)                                  # [cout, kh, kw, cin]: k = (ky*kw + kx)*cin + c
         if k_pad:                                                  # stem: taps*cin = 147 -> 192
@@ -121,19 +146,23 @@ class ResNet(nn.Module):
             out = torch.zeros(cout_pad, kh, kw, cin_pad, dtype=F32, device=w.device)
             out[:cout, :, :, :cin] = w
             out = out.reshape(cout_pad, kh * kw * cin_pad)
-        b = torch.zeros(cout_pad, dtype=F32, device=w.device)
-        b[:cout] = bias
-        return out.to(BF16).contiguous(), b.contiguous()
+        return out.to(BF16).contiguous()
+
+    def _cache_key(self):
+        from .arena import _OPT_STEPS
+        return (sum(p._version for p in self.parameters()) + sum(b._version for b in self.buffers()) + _OPT_STEPS[0],
+                next(self.parameters()).device)
 
     def _prepare(self):
-        from .arena import _OPT_STEPS
-        key = (sum(p._version for p in self.parameters()) + sum(b._version for b in self.buffers()) + _OPT_STEPS[0],
-               next(self.parameters()).device)
+        key = self._cache_key()
         if self.training:
-            raise RuntimeError("icka_amd ResNet runs eval-mode BatchNorm only (call .eval(); the reference keeps the "
-                               "encoder frozen)")
-        if self._folded is not None and self._folded_key == key:
+            if not self.train_batchnorm:
+                raise RuntimeError("icka_amd ResNet runs eval-mode BatchNorm only (call .eval(), or build the network with "
+                                   "train_batchnorm=True for nn.BatchNorm2d's training mode)")
+            return self._prepare_train(key)
+        if self._folded is not None and self._folded_key == key and not (self._bn_moved or self._bn_graphed):
             return self._folded
+        self._bn_moved = False
         plan = {"stem": self._fold(self.conv1, self.bn1, 3, 64, k_pad=192), "blocks": []}
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for blk in layer:
@@ -148,6 +177,110 @@ class ResNet(nn.Module):
                 plan["blocks"].append(entry)
         self._folded, self._folded_key = plan, key
         return plan
+
+    def _prepare_train(self, key):
+        """Unfolded bf16 conv weights of the train-mode path, cached like the fold (same key), each with its BatchNorm."""
+        if self._train_w is not None and self._train_w_key == key:
+            return self._train_w
+        for name, m in self.named_modules():
+            if isinstance(m, nn.BatchNorm2d):
+                if not m.track_running_stats or m.running_mean is None or m.num_batches_tracked is None:
+                    raise NotImplementedError("train-mode BatchNorm needs track_running_stats=True (%s)" % (name or "bn"))
+                if not m.affine or m.weight is None:
+                    raise NotImplementedError("train-mode BatchNorm needs affine=True (%s)" % (name or "bn"))
+
+        def conv(c: nn.Conv2d, bn: nn.BatchNorm2d, cin_pad: int, k_pad: int = 0):
+            if _padc(c.out_channels) != c.out_channels:
+                raise NotImplementedError("train-mode BatchNorm: %d output channels (multiples of 64 up to 64, else 128)"
+                                          % c.out_channels)
+            return self._gemm_weight(c.weight.detach().float(), cin_pad, c.out_channels, k_pad), bn
+
+        plan = {"stem": conv(self.conv1, self.bn1, 3, k_pad=192), "blocks": []}
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in layer:
+                cin, p, cout = blk.conv1.in_channels, blk.conv1.out_channels, blk.conv3.out_channels
+                entry = {"stride": blk.stride, "p": _padc(p), "cout": _padc(cout), "cin": _padc(cin),
+                         "c1": conv(blk.conv1, blk.bn1, _padc(cin)), "c2": conv(blk.conv2, blk.bn2, _padc(p)),
+                         "c3": conv(blk.conv3, blk.bn3, _padc(p)), "down": None}
+                if blk.downsample is not None:
+                    entry["down"] = conv(blk.downsample[0], blk.downsample[1], _padc(cin))
+                plan["blocks"].append(entry)
+        self._train_w, self._train_w_key = plan, key
+        return plan
+
+    @staticmethod
+    def _bn_scale_shift(part: torch.Tensor, bn: nn.BatchNorm2d, rows_valid: int):
+        """Batch statistics -> (scale, shift); running statistics updated on the device (nn.BatchNorm2d.forward in training)."""
+        if rows_valid < 2:
+            raise ValueError("Expected more than 1 value per channel when training, got %d" % rows_valid)
+        return K.bn_finalize(part, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
+                             bn.num_batches_tracked, bn.momentum, bn.eps)
+
+    def _features_train(self, x: torch.Tensor, plan) -> Tuple[torch.Tensor, int, int, int]:
+        """features() with train-mode BatchNorm: per BN'd convolution a statistics GEMM (raw output + tile partials), a
+        finalise launch and an apply launch (scale, shift, residual, ReLU; zeros at the padded rows)."""
+        B, _, H, W = x.shape
+        dev = x.device
+        lib = K._lib.load()
+        st = K._stream
+        zeros = self._zero_page(dev)
+        Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+        rv = B * Ho * Wo
+        rows = _pad128(rv)
+        patches = torch.empty(rows, 192, dtype=BF16, device=dev)
+        K.check(lib.icka_conv_stem_patches(x.data_ptr(), patches.data_ptr(), B, H, W, rows, st()), "icka_conv_stem_patches")
+        w, bn = plan["stem"]
+        raw, part = K.gemm_bn_stats(patches, w, rv)                             # conv1 (:139)
+        sc, sh = self._bn_scale_shift(part, bn, rv)                             # bn1 (:140)
+        cur = K.bn_apply(raw, sc, sh, rv, nbt=(bn.num_batches_tracked,))        # relu (:141)
+        Hc, Wc = (Ho + 2 - 3) // 2 + 1, (Wo + 2 - 3) // 2 + 1
+        rows = _pad128(B * Hc * Wc)
+        pooled = torch.empty(rows, 64, dtype=BF16, device=dev)
+        K.check(lib.icka_conv_maxpool3x3s2(cur.data_ptr(), pooled.data_ptr(), B, Ho, Wo, 64, rows, st()),
+                "icka_conv_maxpool3x3s2")                                        # maxpool (:142)
+        cur = pooled
+        for e in plan["blocks"]:                                                 # Bottleneck.forward (:74-93)
+            s = e["stride"]
+            rv = B * Hc * Wc
+            w, bn = e["c1"]
+            raw, part = K.gemm_bn_stats(cur, w, rv)
+            sc, sh = self._bn_scale_shift(part, bn, rv)
+            t1 = K.bn_apply(raw, sc, sh, rv, nbt=(bn.num_batches_tracked,))
+            Hn, Wn = (Hc + 2 - 3) // s + 1, (Wc + 2 - 3) // s + 1
+            rv_out = B * Hn * Wn
+            rows_out = _pad128(rv_out)
+            w, bn = e["c2"]
+            if self.implicit_conv:
+                raw, part = K.conv3x3_bn_stats(t1, w, B, Hc, Wc, e["p"], e["p"], s, rows_out, zeros)
+            else:
+                pm = torch.empty(rows_out, 9 * e["p"], dtype=BF16, device=dev)
+                K.check(lib.icka_conv_im2col3x3(t1.data_ptr(), pm.data_ptr(), B, Hc, Wc, e["p"], s, rows_out, st()),
+                        "icka_conv_im2col3x3")
+                raw, part = K.gemm_bn_stats(pm, w, rv_out)
+            sc, sh = self._bn_scale_shift(part, bn, rv_out)
+            t2 = K.bn_apply(raw, sc, sh, rv_out, nbt=(bn.num_batches_tracked,))
+            w, bn3 = e["c3"]
+            raw3, part = K.gemm_bn_stats(t2, w, rv_out)
+            if e["down"] is not None:
+                xs = cur
+                if s != 1:
+                    xs = torch.empty(rows_out, e["cin"], dtype=BF16, device=dev)
+                    K.check(lib.icka_conv_subsample(cur.data_ptr(), xs.data_ptr(), B, Hc, Wc, e["cin"], s, rows_out, st()),
+                            "icka_conv_subsample")
+                wd, bnd = e["down"]
+                rawd, partd = K.gemm_bn_stats(xs, wd, rv_out)
+                scd, shd = self._bn_scale_shift(partd, bnd, rv_out)
+                sc, sh = self._bn_scale_shift(part, bn3, rv_out)
+                cur = K.bn_apply(raw3, sc, sh, rv_out, residual=rawd, res_scale=scd, res_shift=shd,
+                                 nbt=(bn3.num_batches_tracked, bnd.num_batches_tracked))
+            else:
+                sc, sh = self._bn_scale_shift(part, bn3, rv_out)
+                cur = K.bn_apply(raw3, sc, sh, rv_out, residual=cur, nbt=(bn3.num_batches_tracked,))
+            Hc, Wc = Hn, Wn
+        self._bn_moved = True
+        if torch.cuda.is_current_stream_capturing():
+            self._bn_graphed = True
+        return cur, B, Hc, Wc
 
     def _zero_page(self, dev):
         z = getattr(self, "_zeros", None)
@@ -164,6 +297,8 @@ class ResNet(nn.Module):
             raise ValueError("expected images [B,3,H,W]")
         plan = self._prepare()
         x = x.float().contiguous()
+        if self.training:
+            return self._features_train(x, plan)
         B, _, H, W = x.shape
         dev = x.device
         lib = K._lib.load()
@@ -237,7 +372,8 @@ def resnet152(pretrained=False, **kwargs):
 
 class myResnet(nn.Module):
     """resnet/resnet_utils.py:6-53.  forward(x, att_size=7) -> (x [B,2048], fc [B,2048], att [B,2048,7,7]), all f32.
-    ``last_tokens`` keeps the same features as bf16 region tokens [B*49, 2048] for the MNER trunk."""
+    ``last_tokens`` keeps the same features as bf16 region tokens [B*49, 2048] for the MNER trunk.  A network built with
+    ``train_batchnorm=True`` runs train-mode BatchNorm while it is in ``.train()``."""
 
     def __init__(self, resnet, if_fine_tune=False, device=None):
         super().__init__()

@@ -610,6 +610,29 @@ int icka_conv_maxpool3x3s2(const void* src, void* dst, int32_t B, int32_t H, int
                            void* stream);
 int icka_conv_features_out(const void* x, float* att, float* fc, void* tokens, int32_t B, int32_t P, int32_t C,
                            void* stream);
+/* Train-mode BatchNorm of the ResNet encoder (nn.BatchNorm2d in training mode, track_running_stats=True; ResNet(...,
+ * train_batchnorm=True)).  Each BN'd convolution runs as three launches:
+ *  1. icka_gemm_bn_stats (1x1 convolutions, stem patch GEMM: y = a . w^T, a bf16 [M, lda], w bf16 [N, ldw], NT) or
+ *     icka_conv3x3_gemm_stats (the implicit 3x3 convolution, arguments as icka_conv3x3_gemm): writes the RAW output bf16
+ *     [M, N] (no bias, no activation) and, from the f32 accumulators, partials f32 [3][M / 128][N] = (count, mean, M2) of
+ *     every (128-row tile, channel) over the rows m < rows_valid.  M % 128 == 0, N % 64 == 0, K % 64 == 0.
+ *  2. icka_bn_finalize: merges the tiles' partials per channel in a fixed order (Chan's parallel variance), then
+ *     scale = weight / sqrt(var + eps), shift = bias - mean * scale, running_mean / running_var <- (1 - m) * old + m * (mean,
+ *     var * n / (n - 1)), m = momentum, or 1 / (num_batches_tracked + 1) when momentum < 0 (momentum=None).  In place on the
+ *     device: graph-capturable, no host synchronisation.
+ *  3. icka_bn_apply: y = [relu](raw * scale + shift [+ r]) on rows < rows_valid, zeros on [rows_valid, rows_padded); r =
+ *     residual (bf16), or residual * res_scale + res_shift when res_scale is given (the downsample branch); y may be raw.
+ *     Adds 1 to *nbt_a and *nbt_b (int64 num_batches_tracked, each nullable): the increment of the BatchNorms it applies. */
+int icka_gemm_bn_stats(const void* a, int64_t lda, const void* w, int64_t ldw, void* y, int64_t ldy, int32_t M, int32_t N, int32_t K,
+                       int64_t rows_valid, float* partials, void* stream);
+int icka_conv3x3_gemm_stats(const void* x, const void* w, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Cout,
+                            int32_t stride, int64_t rows_padded, const void* zeros, float* partials, void* stream);
+int icka_bn_finalize(const float* partials, int32_t tiles, int32_t C, const float* weight, const float* bias, float* running_mean,
+                     float* running_var, const int64_t* num_batches_tracked, float momentum, float eps, float* scale, float* shift,
+                     void* stream);
+int icka_bn_apply(const void* raw, const float* scale, const float* shift, const void* residual, const float* res_scale,
+                  const float* res_shift, void* y, int32_t C, int64_t rows_valid, int64_t rows_padded, int32_t relu, int64_t* nbt_a,
+                  int64_t* nbt_b, void* stream);
 /* Dropout nonce for hipGraph replay.  Every dropout-bearing kernel XORs two DEVICE words into its (by-value) seed at
  * entry when a nonce is registered.  A captured graph re-launches the same seed values, so the graph also captures
  * icka_bump_dropout_nonce at the start of a step: each replay then draws fresh masks, and the forward and backward
