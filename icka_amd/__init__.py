@@ -20,6 +20,8 @@ from . import cross_modal
 from .cross_modal import PromptRobertaModel
 from . import packing
 from .packing import PackOverflowError, TokenBudgetBatchSampler, set_packed
+from . import metrics
+from .metrics import ChunkEvaluator
 
 __all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "BertConfig", "BertModel", "BertEmbeddings", "BertEncoder", "BertLayer", "BertLayerNorm", "BertPooler",
            "BertSelfEncoder", "BertCrossEncoder", "BertCrossAttentionLayer", "BertAttention", "BertCrossAttention",
@@ -27,4 +29,4 @@ __all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "Bert
            "BertPreTrainedModel", "MTCCMBertForMMTokenClassificationCRF", "cls_layer_both", "scalar_gate_fusion",
            "token_ce_loss", "set_precision", "resolved_precision", "ParamArena", "cross_modal", "PromptRobertaModel",
            "GradReducer", "graph", "DevicePrefetcher", "GraphedModule", "GraphedStep", "packing", "set_packed",
-           "PackOverflowError", "TokenBudgetBatchSampler"]
+           "PackOverflowError", "TokenBudgetBatchSampler", "metrics", "ChunkEvaluator"]

@@ -55,7 +55,9 @@ def split_tags(lens: Sequence[int], flat: Sequence[int]) -> List[List[int]]:
 class DeviceTags(object):
     """Viterbi paths kept on the device (``icka_crf_score_decode``): ``lens`` int32 [B] and ``tags_flat`` int32 [>= B*S], the
     paths back to back.  ``tolist()`` gives what ``CRF.decode`` returns.  ``DeviceTags.empty`` puts both in one buffer so that
-    ``tolist()`` is one device-to-host copy."""
+    ``tolist()`` is one device-to-host copy.  ``deferred_check`` (None or a callable): the error check the producer did NOT run
+    because it did not sync the host (``GraphedModule(decode="device")``); whoever reads results derived from these tags back
+    calls it after that copy (``metrics.ChunkEvaluator.compute`` does)."""
 
     def __init__(self, lens: torch.Tensor, tags_flat: torch.Tensor, _joint: Optional[torch.Tensor] = None):
         for n, t in (("lens", lens), ("tags_flat", tags_flat)):
@@ -69,6 +71,7 @@ class DeviceTags(object):
         self.lens = lens
         self.tags_flat = tags_flat
         self._joint = _joint
+        self.deferred_check = None
 
     @classmethod
     def empty(cls, B: int, S: int, device) -> "DeviceTags":

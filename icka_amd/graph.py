@@ -772,6 +772,13 @@ class _ModuleCapture(_StepBase):
 
     def run(self, values) -> torch.Tensor:
         self._prepare(self.gf is None, values, flags=self.reducer is not None)
+        if self._tags is not None and self.owner.decode == "device":
+            # decode="device": the static DeviceTags itself, no copy and no sync; the error words of THIS replay are read by
+            # whoever syncs next (DeviceTags.deferred_check), at the latest before the next replay (_prepare)
+            self.gf.replay()
+            if self._tags.deferred_check is None:      # (set once: the evaluator keeps one entry per distinct check)
+                self._tags.deferred_check = self._deferred_check
+            return self._tags if self.out is None else (self._tags, self.out.detach())
         if self._tags is not None:              # decode=True: what the eager model returns -- lists, or (lists, loss)
             self.gf.replay()
             tags = self._tags.tolist()          # (the one host sync of the call)
@@ -784,10 +791,19 @@ class _ModuleCapture(_StepBase):
         self.gf.replay()
         return self.out.detach()
 
+    def _deferred_check(self) -> None:
+        K.lstm_check_error(self._detected)
+        K.gemm_ln_check_error(self._detected)
+
     def close(self) -> None:
         self._close_nonce()
         self.gf = None
         self._bwd = {}
+
+
+def _eager_deferred_check() -> None:
+    K.lstm_check_error("detected after an eager GraphedModule(decode=\"device\") call")
+    K.gemm_ln_check_error("detected after an eager GraphedModule(decode=\"device\") call")
 
 
 class GraphedModule(object):
@@ -833,10 +849,18 @@ class GraphedModule(object):
     call sites decode with ``icka_crf_score_decode`` into a ``crf.DeviceTags`` (the dev loss from the same launch); such calls are
     captured and replayed like any other, under the same cache key, and each replay returns the lists (``tolist()``: one
     device-to-host copy) or ``(lists, loss)`` -- the types the eager model returns (the loss is the static output, as above).
-    Calls past ``max_captures``, or whose capture fails, still run eagerly and return the eager model's lists."""
+    Calls past ``max_captures``, or whose capture fails, still run eagerly and return the eager model's lists.
+
+    ``decode="device"``: as ``decode=True``, but a decoding call -- replayed or run eagerly -- returns the ``DeviceTags`` itself
+    (``(DeviceTags, loss)`` for ``mode="dev"``): no ``tolist()``, no host sync.  On a replay both are the capture's STATIC
+    buffers, valid until the next call of the same capture; work enqueued on the stream before that call
+    (``metrics.ChunkEvaluator.update`` / ``add_loss``) reads them in stream order.  The check of the BiLSTM hand-off and fused
+    dense + LayerNorm error words that ``decode=True`` runs after its sync is deferred: the returned ``DeviceTags`` carries it
+    as ``deferred_check``, ``ChunkEvaluator.update`` keeps it and ``compute()`` runs it right after its one device-to-host
+    copy, so metrics are never built silently from NaN emissions (the next replay's own preamble checks the words too)."""
 
     def __init__(self, module: torch.nn.Module, example_args=(), example_kwargs=None, warmup: int = 3, reducer=None,
-                 accumulate: int = 1, max_captures: int = 4, decode: bool = False):
+                 accumulate: int = 1, max_captures: int = 4, decode=False):
         if accumulate < 1:
             raise ValueError("accumulate must be >= 1")
         if max_captures < 1:
@@ -854,7 +878,7 @@ class GraphedModule(object):
         d["reducer"] = reducer
         d["accumulate"] = int(accumulate)
         d["max_captures"] = int(max_captures)
-        d["decode"] = bool(decode)
+        d["decode"] = "device" if (isinstance(decode, str) and decode == "device") else bool(decode)
         d["_warmup"] = warmup
         d["_cycle"] = _Cycle(int(accumulate)) if reducer is not None else None
         d["_caps"] = {}
@@ -958,7 +982,14 @@ class GraphedModule(object):
     # ---- eager calls (past the cache, un-capturable signatures)
     def _eager(self, args, kwargs):
         self.stats["eager_calls"] += 1
-        out = self.model(*args, **kwargs)
+        if self.decode == "device":
+            with crf.device_decode():
+                out = self.model(*args, **kwargs)
+            tags = out[0] if isinstance(out, tuple) else out
+            if isinstance(tags, crf.DeviceTags):
+                tags.deferred_check = _eager_deferred_check
+        else:
+            out = self.model(*args, **kwargs)
         if self.reducer is None or not (torch.is_grad_enabled() and isinstance(out, torch.Tensor) and out.requires_grad):
             return out
         return _EagerTail.apply(out, self)

@@ -962,6 +962,56 @@ def check_flat_tags(lens, tags_flat, B, S):
         raise ValueError("tags_flat holds %d tags, a batch of %d x %d needs up to %d" % (tags_flat.numel(), B, S, B * S))
 
 
+# ------------------------------------------------------------------------------------------------- chunk metrics
+CHUNK_EVAL_MAX_S, CHUNK_EVAL_MAX_IDS, CHUNK_EVAL_MAX_TYPES, CHUNK_EVAL_HEAD = 512, 64, 32, 6
+
+
+def chunk_eval(labels, output_mask, label_table, counters, ntypes, *, lens=None, tags_flat=None, pred=None):
+    """Add the chunk-level counts of one batch into ``counters`` (icka_chunk_eval, include/icka_hip.h): one launch, no host
+    sync.  Predictions either as ``lens`` + ``tags_flat`` (a ``crf.DeviceTags``) or as ``pred`` int64 [B, S]."""
+    _dev(labels, "labels")
+    if labels.dim() != 2:
+        raise ValueError("labels must be [B, S], got %s" % (tuple(labels.shape),))
+    B, S = labels.shape
+    _i64(labels, "labels", (B, S)); _i64(output_mask, "output_mask", (B, S))
+    if not 1 <= S <= CHUNK_EVAL_MAX_S or B < 1:
+        raise ValueError("chunk_eval: B >= 1 and 1 <= S <= %d, got [%d, %d]" % (CHUNK_EVAL_MAX_S, B, S))
+    _dev(label_table, "label_table"); _dev(counters, "counters")
+    L = label_table.numel()
+    if label_table.dtype != torch.int32 or label_table.dim() != 1 or not label_table.is_contiguous() \
+            or not 1 <= L <= CHUNK_EVAL_MAX_IDS:
+        raise ValueError("label_table must be a contiguous int32 vector of 1 .. %d words" % CHUNK_EVAL_MAX_IDS)
+    if not 1 <= ntypes <= CHUNK_EVAL_MAX_TYPES:
+        raise ValueError("chunk_eval: 1 <= ntypes <= %d, got %d" % (CHUNK_EVAL_MAX_TYPES, ntypes))
+    if counters.dtype != torch.int64 or counters.dim() != 1 or not counters.is_contiguous() \
+            or counters.numel() < CHUNK_EVAL_HEAD + 3 * ntypes:
+        raise ValueError("counters must be a contiguous int64 vector of at least %d entries" % (CHUNK_EVAL_HEAD + 3 * ntypes))
+    if (lens is None) != (tags_flat is None) or (lens is None) == (pred is None):
+        raise ValueError("chunk_eval: predictions as lens + tags_flat or as pred, not both")
+    cap = 0
+    if lens is not None:
+        check_flat_tags(lens, tags_flat, B, 0)
+        _dev(lens, "lens"); _dev(tags_flat, "tags_flat")
+        cap = tags_flat.numel()
+    else:
+        _dev(pred, "pred")
+        if pred.dtype != torch.int64 or tuple(pred.shape) != (B, S) or (S > 1 and pred.stride(1) != 1) or pred.stride(0) < S:
+            raise ValueError("pred must be int64 [%d, %d] with unit column stride" % (B, S))
+    check(_lib.load().icka_chunk_eval(_ptr(lens), _ptr(tags_flat), cap, _ptr(pred), _ld(pred), labels.data_ptr(),
+                                      output_mask.data_ptr(), label_table.data_ptr(), counters.data_ptr(), B, S, L,
+                                      int(ntypes), _stream()), "icka_chunk_eval")
+
+
+def loss_accumulate(loss, acc):
+    """acc[0] += loss, acc[1] += 1 on the device (icka_loss_accumulate): ``loss`` one f32 element, ``acc`` f64 [2]."""
+    _dev(loss, "loss"); _dev(acc, "acc")
+    if loss.dtype != F32 or loss.numel() != 1:
+        raise ValueError("loss must hold one f32 element, got %s %s" % (loss.dtype, tuple(loss.shape)))
+    if acc.dtype != torch.float64 or acc.numel() != 2 or not acc.is_contiguous():
+        raise ValueError("acc must be a contiguous f64 vector of 2")
+    check(_lib.load().icka_loss_accumulate(loss.data_ptr(), acc.data_ptr(), _stream()), "icka_loss_accumulate")
+
+
 # ------------------------------------------------------------------------------------------------- helpers
 def cast_f32_to_bf16(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     _dev(src, "src"); _dev(dst, "dst")

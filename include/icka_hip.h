@@ -528,6 +528,34 @@ int icka_crf_score_decode(const float* emissions, int64_t ld, const int64_t* tag
                           const float* start, const float* end, const float* trans, float* llh, int32_t* lens,
                           int32_t* tags_flat, int64_t capacity, int32_t B, int32_t S, int32_t C, void* stream);
 /* ---------------------------------------------------------------------------------------------------------------
+ * Chunk-level scoring of a dev / test batch (csrc/metrics.hip): the counts behind the reference's accuracy / precision /
+ * recall / F1, overall and per entity type -- the per-token loop of My_cross_attention.py:882-903 followed by
+ * ner_evaluate.py:4-148 (get_chunks, evaluate, evaluate_each_class).  One launch ADDS the batch's counts into
+ *   counters int64 [6 + 3 * ntypes] = kept_tokens, equal_tokens, correct_preds, total_preds, total_correct, bad_ids,
+ *                                     then (correct, preds, golds) per type id
+ * with 64-bit atomic adds (integer sums: independent of the order, a graph replay equals an eager call).  No host sync.
+ * Predictions in ONE of two forms: lens int32 [B] + tags_flat int32 [capacity], the paths back to back as
+ * icka_crf_score_decode writes them (path b starts at sum(lens[0 .. b-1]), summed inside the kernel; pred NULL), or
+ * pred int64 [B,S] with row stride ld_pred >= S (lens and tags_flat NULL).  labels, output_mask int64 [B,S] contiguous
+ * (mask: zero / non-zero).  label_table int32 [L], one word per tag id: bit 0 = the default tag ("O"), bit 1 = class "B"
+ * (name.split('-')[0] == "B"), bit 2 = skipped when it is the GOLD label (the reference's X, </s>, <s>, [CLS], [SEP]),
+ * bits 8.. = type id < ntypes (name.split('-')[-1]).  1 <= S <= 512, L <= 64, ntypes <= 32, any B >= 1.
+ * Per sample: the kept positions are j < n0 (n0 = index of the first zero of output_mask[b]) whose gold label has no
+ * skip bit, compacted in order; the prediction at j is path_b[j] / pred[b,j].  On the compacted gold and predicted
+ * sequences separately, O(i) = default tag, t(i) = type id: start(i) = !O(i) && (i == 0 || O(i-1) || t(i) != t(i-1) ||
+ * B(i)), term(i) = O(i) || start(i); a chunk begins at every start, has that token's type and ends at the next term
+ * (or the end).  total_preds / total_correct += predicted / gold starts (per type too); correct_preds += positions
+ * where both start with one type and both chunks end at the same index (per type: under that type); kept_tokens +=
+ * kept positions, equal_tokens += those with pred == gold.  A sample whose path is shorter than n0, or with a gold id
+ * at j < n0 or a predicted id at a kept position outside [0, L) (never used as an index), adds 1 to bad_ids and
+ * nothing else. */
+int icka_chunk_eval(const int32_t* lens, const int32_t* tags_flat, int64_t capacity, const int64_t* pred, int64_t ld_pred,
+                    const int64_t* labels, const int64_t* output_mask, const int32_t* label_table, int64_t* counters,
+                    int32_t B, int32_t S, int32_t L, int32_t ntypes, void* stream);
+/* acc[0] += (double)loss[0], acc[1] += 1 (one launch, stream-ordered): the dev loop's `dev_total_loss += loss.item();
+ * index += 1` (My_cross_attention.py:877-878) without the host sync.  loss f32 [1], acc f64 [2]. */
+int icka_loss_accumulate(const float* loss, double* acc, void* stream);
+/* ---------------------------------------------------------------------------------------------------------------
  * Bidirectional single-layer LSTM of the tagging tail:
  * nn.LSTM(H, H, batch_first=True, bidirectional=True) at Cross_Modal_Interaction_Module.py:905-908, called :1042
  * (`x, _ = self.lstm(result)`).  Gate order i, f, g, o as torch.nn.LSTM.  The input projection (x . W_ih^T + b_ih +
