@@ -67,6 +67,7 @@ PROTOTYPES = {
     "icka_gemm": (c_i32, [C.POINTER(GemmDesc), c_vp]),
     "icka_gemm_grouped": (c_i32, [C.POINTER(GemmDesc), c_i32, c_vp]),
     "icka_gemm_grouped_ex": (c_i32, [C.POINTER(GemmDesc), c_i32, C.POINTER(SlabReduction), c_i32, c_vp]),
+    "icka_gemm_grouped_live": (c_i32, [C.POINTER(GemmDesc), c_i32, C.POINTER(SlabReduction), c_i32, C.POINTER(c_vp), c_vp]),
     "icka_gemm_ln": (c_i32, [C.POINTER(GemmDesc), c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_f32,
                              c_f32, c_u64, c_vp, c_vp, c_vp]),
     "icka_gemm_qkv_attn": (c_i32, [C.POINTER(GemmDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_u64, c_vp, c_vp]),
@@ -81,6 +82,8 @@ PROTOTYPES = {
                             c_vp, c_i32, c_i32, c_f32, c_u64, c_i32, c_vp]),
     "icka_ln_bwd_slabs": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32,
                                   c_i32, c_f32, c_u64, c_vp]),
+    "icka_ln_bwd_slabs_live": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                       c_vp, c_i32, c_i32, c_i32, c_f32, c_u64, c_vp]),
     "icka_ln_bwd_nslab": (c_i32, [c_i32]),
     "icka_ln_slab_slots": (c_i32, []),
     "icka_embed_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,

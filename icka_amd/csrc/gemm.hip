@@ -436,6 +436,15 @@ __device__ __forceinline__ void dma_issue(const bf16_t* (&ptr)[4], int64_t strid
     for (int j = 0; j < 4; ++j) ptr[j] += stride;
 }
 
+// The same 4 loads from ptr + off, the pointers left where they are (the live-tile loader: k-tiles are not visited in
+// unit steps, so the tile's operand offset replaces the running stride).
+__device__ __forceinline__ void dma_issue_at(const bf16_t* const (&ptr)[4], int64_t off, uint32_t lds_base) {
+    const bf16_t* q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = ptr[j] + off;
+    dma_issue(q, 0, lds_base);
+}
+
 // f32 C tile in LDS: [128 rows][32 chunks of 4 floats], chunk index XORed with row&31
 __device__ __forceinline__ uint32_t off_c(int row, int ch) { return row * 512 + ((ch ^ (row & 31)) << 4); }
 // same for a 192-column f32 tile (48 chunks of 16 B per row; the XOR stays inside each group of 16 chunks)
@@ -1876,10 +1885,12 @@ int launch(GemmArgs g, bool aligned, hipStream_t st, const Tune& t) {
         // blockIdx.y and accumulate f32 partial tiles atomically (C is scaled by beta / zeroed first)
         const int nk = (g.K + BK - 1) / BK;
         int ks = 1;
-        // (M <= 256 only: weight-gradient shapes.  Forward outputs such as the [tokens, labels] emissions stay on one
+        // (TN with M <= 256 only: weight-gradient shapes.  Forward outputs such as the [tokens, labels] emissions stay on one
         //  block per tile so that two identical calls give bitwise identical logits -- atomic split-K order flipped
-        //  Viterbi near-ties between a 'dev' and a 'test' pass of the same batch.)
-        if (g.c_f32 && g.epi == ICKA_EPI_NONE && nb < 64 && nk >= 16 && g.M <= 256 && !g.C3) {   // (a wire copy needs the final value in one epilogue)
+        //  Viterbi near-ties between a 'dev' and a 'test' pass of the same batch.  M <= 256 alone is not that rule: an NT
+        //  forward GEMM of a few ROWS -- [batch, 1024] x [1024, 1024] with f32 output at eval batch 2 or 3 -- met it too, and
+        //  its 4 atomically added partials made the dev loss of a replayed capture differ from the eager one in the last bits.)
+        if (A_KM && B_KM && g.c_f32 && g.epi == ICKA_EPI_NONE && nb < 64 && nk >= 16 && g.M <= 256 && !g.C3) {   // (a wire copy needs the final value in one epilogue)
             ks = 256 / nb;
             if (ks > nk / 4) ks = nk / 4;
             if (ks < 1) ks = 1;
@@ -2262,6 +2273,52 @@ struct BigGroupArgs {
     int cs_start[MAX_GROUP + 1];  // first column-sum block of each problem (relative to the total tiles)
     SlabRed red[MAX_RED];         // slab reductions riding on the launch (LayerNorm dgamma / dbeta of the layer)
     int red_start[MAX_RED + 1];   // first block of each reduction (relative to tiles + column-sum blocks)
+    const uint8_t* k_live[MAX_GROUP];   // LIVE instances: K bytes per problem, byte t == 0 -> row t of an operand is all zero
+};
+
+// Live k-tiles of one problem (LIVE instances of the 12-wave body).  k-tile i is live if any of its 64 flag bytes is set;
+// lane i ORs the 64 bytes of k-tile base + i (four 16-byte loads) and a ballot gives the wave-uniform word of 64 k-tiles.
+// Every wave of the block builds the words from the same bytes (written by an earlier kernel of the stream, not during
+// the launch), so loader and compute waves walk the same tiles in the same ascending order and their barrier counts
+// agree by construction.  A null pointer means every row is live.
+struct LiveTiles {
+    const uint8_t* flags;
+    int nk, base, lane;
+    uint64_t word;
+    __device__ __forceinline__ uint64_t load_word() const {
+        uint32_t any = 0u;
+        const int t = base + lane;
+        if (t < nk) {
+            any = 1u;
+            if (flags) {
+                const u32x4* q = reinterpret_cast<const u32x4*>(flags + (int64_t)t * BK);
+                const u32x4 v = (q[0] | q[1]) | (q[2] | q[3]);
+                any = (v[0] | v[1]) | (v[2] | v[3]);
+            }
+        }
+        return __ballot(any != 0u);
+    }
+    __device__ __forceinline__ LiveTiles(const uint8_t* f, int nk_, int lane_) : flags(f), nk(nk_), base(0), lane(lane_) {
+        word = load_word();
+    }
+    // number of live k-tiles: what next() returns before it returns -1
+    static __device__ __forceinline__ int count(const uint8_t* f, int nk, int lane) {
+        LiveTiles lt(f, nk, lane);
+        int n = __builtin_popcountll(lt.word);
+        for (lt.base = 64; lt.base < nk; lt.base += 64) n += __builtin_popcountll(lt.load_word());
+        return n;
+    }
+    // next live k-tile in ascending order, -1 when there is none left
+    __device__ __forceinline__ int next() {
+        while (word == 0) {
+            if (base + 64 >= nk) return -1;
+            base += 64;
+            word = load_word();
+        }
+        const int kt = base + __builtin_ctzll(word);
+        word &= word - 1;
+        return kt;
+    }
 };
 
 // 64 output values per block (8 slab lanes x 64 columns), fixed summation order: bitwise reproducible
@@ -2497,8 +2554,12 @@ __device__ __forceinline__ void big_colsum_block(const GemmArgs& g, char* smem, 
 // 12-wave form of the same tile (8 compute waves of 64 x 64, two per SIMD, + 4 loader waves): fragments are read per
 // 32-deep step right before their MFMAs and the second compute wave of the SIMD covers the LDS (ds_read_b64_tr_b16)
 // latency, instead of one wave per SIMD with software-pipelined register sets.
-template <bool WIRE>
-__device__ __forceinline__ void gemm_big12_tn_body(const GemmArgs& g, char* smem, const int m0, const int n0) {
+// LIVE: the reduction runs over the live k-tiles of ``k_live`` only (LiveTiles).  A skipped tile has an all-zero operand
+// tile, so the full reduction would add only +-0 products to accumulators that started at +0: the result is bitwise the
+// full one whenever the other operand is finite.  No live tile at all: nothing is staged and the epilogue writes beta * C.
+template <bool WIRE, bool LIVE = false>
+__device__ __forceinline__ void gemm_big12_tn_body(const GemmArgs& g, char* smem, const int m0, const int n0,
+                                                   const uint8_t* k_live = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(LDS_PTR(char, smem)));
@@ -2518,6 +2579,39 @@ __device__ __forceinline__ void gemm_big12_tn_body(const GemmArgs& g, char* smem
         dma_issue(pa1, sa, lds0 + (BUF) + TILE_BYTES + lw * 1024);       \
         dma_issue(pb, sb, lds0 + (BUF) + 2 * TILE_BYTES + lw * 1024);    \
     } while (0)
+        if constexpr (LIVE) {
+            // the same ring, over the live tiles: the pointers stay at k-tile 0 and every stage adds its tile's offset
+            static_assert(BIG_NBUF == 3, "the live-tile loader keeps two tiles in flight");
+#define ICKA_BIG_STAGE_AT(BUF, KT)                                                       \
+    do {                                                                                 \
+        const int64_t oa = (KT) * sa, ob = (KT) * sb;                                    \
+        dma_issue_at(pa0, oa, lds0 + (BUF) + lw * 1024);                                 \
+        dma_issue_at(pa1, oa, lds0 + (BUF) + TILE_BYTES + lw * 1024);                    \
+        dma_issue_at(pb, ob, lds0 + (BUF) + 2 * TILE_BYTES + lw * 1024);                 \
+    } while (0)
+            LiveTiles lt(k_live, nk, lane);
+            int t0 = lt.next();
+            int t1 = t0 >= 0 ? lt.next() : -1;
+            if (t0 >= 0) ICKA_BIG_STAGE_AT(0, t0);
+            if (t1 >= 0) ICKA_BIG_STAGE_AT(BIG_STAGE, t1);
+            int cur = 0;
+            while (t0 >= 0) {   // one barrier per live tile, as in the compute waves
+                const int t2 = t1 >= 0 ? lt.next() : -1;
+                if (t1 >= 0) wait_vmcnt<12>();
+                else wait_vmcnt<0>();
+                __builtin_amdgcn_s_barrier();
+                if (t2 >= 0) {
+                    int nx = cur + BIG_NBUF - 1;
+                    nx = nx >= BIG_NBUF ? nx - BIG_NBUF : nx;
+                    ICKA_BIG_STAGE_AT(nx * BIG_STAGE, t2);
+                }
+                cur = cur + 1 == BIG_NBUF ? 0 : cur + 1;
+                t0 = t1;
+                t1 = t2;
+            }
+#undef ICKA_BIG_STAGE_AT
+            return;
+        }
 #pragma unroll
         for (int t = 0; t < BIG_NBUF - 1; ++t)
             if (t < nk) ICKA_BIG_STAGE(t * BIG_STAGE);
@@ -2545,26 +2639,26 @@ __device__ __forceinline__ void gemm_big12_tn_body(const GemmArgs& g, char* smem
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     int cur = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        __builtin_amdgcn_s_barrier();   // tile kt published; this wave is done with tile kt-1
-        asm volatile("" ::: "memory");
-        const char* st = smem + cur * BIG_STAGE;
-        const char* sA = st + (wr >> 7) * TILE_BYTES;
-        const char* sB = st + 2 * TILE_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 fa[4], fb[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) fa[t] = read_frag<true>(sA, (wr & 127) + 16 * t, ks, lane);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) fb[t] = read_frag<true>(sB, wc + 16 * t, ks, lane);
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma16(fb[ni], fa[mi], acc[mi][ni]);
-        }
-        cur = cur + 1 == BIG_NBUF ? 0 : cur + 1;
-    }
+#define ICKA_BIG12_TILE()                                                                                    \
+    do {                                                                                                     \
+        __builtin_amdgcn_s_barrier();   /* next tile published; this wave is done with the one before */     \
+        asm volatile("" ::: "memory");                                                                       \
+        const char* st = smem + cur * BIG_STAGE;                                                             \
+        const char* sA = st + (wr >> 7) * TILE_BYTES;                                                        \
+        const char* sB = st + 2 * TILE_BYTES;                                                                \
+        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                   \
+            bf16x8 fa[4], fb[4];                                                                             \
+            _Pragma("unroll") for (int t = 0; t < 4; ++t) fa[t] = read_frag<true>(sA, (wr & 127) + 16 * t, ks, lane); \
+            _Pragma("unroll") for (int t = 0; t < 4; ++t) fb[t] = read_frag<true>(sB, wc + 16 * t, ks, lane); \
+            _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                                 \
+                _Pragma("unroll") for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma16(fb[ni], fa[mi], acc[mi][ni]); \
+        }                                                                                                    \
+        cur = cur + 1 == BIG_NBUF ? 0 : cur + 1;                                                             \
+    } while (0)
+    // LIVE: the compute waves need only the NUMBER of live tiles -- as many trips (and barriers) as the loader waves make
+    const int ntrip = LIVE ? LiveTiles::count(k_live, nk, lane) : nk;
+    for (int kt = 0; kt < ntrip; ++kt) ICKA_BIG12_TILE();
+#undef ICKA_BIG12_TILE
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
@@ -2583,7 +2677,9 @@ __device__ __forceinline__ void gemm_big12_tn_body(const GemmArgs& g, char* smem
     }
 }
 
-template <bool W12, bool WIRE = false>   // WIRE: some problem of the group writes the data-parallel wire copy (C3)
+// WIRE: some problem of the group writes the data-parallel wire copy (C3); LIVE (12-wave body only): some problem of the
+// group carries row-liveness flags (ga.k_live) and reduces over its live k-tiles only
+template <bool W12, bool WIRE = false, bool LIVE = false>
 __global__ __launch_bounds__(W12 ? 768 : 512) void gemm_big_group_kernel(const BigGroupArgs ga) {
     __shared__ __attribute__((aligned(16))) char smem[BIG_NBUF * BIG_STAGE];
     const int bid = blockIdx.x;
@@ -2623,7 +2719,8 @@ __global__ __launch_bounds__(W12 ? 768 : 512) void gemm_big_group_kernel(const B
     int tm, tn;
     if (nbn > nbm) { tm = local % nbm; tn = local / nbm; }
     else { tm = local / nbn; tn = local % nbn; }
-    if constexpr (W12) gemm_big12_tn_body<WIRE>(g, smem, tm * 256, tn * BN);
+    if constexpr (W12 && LIVE) gemm_big12_tn_body<WIRE, true>(g, smem, tm * 256, tn * BN, ga.k_live[pi]);
+    else if constexpr (W12) gemm_big12_tn_body<WIRE>(g, smem, tm * 256, tn * BN);
     else gemm_big_tn_body<WIRE>(g, smem, tm * 256, tn * BN);
 }
 
@@ -2648,21 +2745,41 @@ static int launch_group(const GroupArgs& ga, int total, hipStream_t st, const Tu
 }
 
 static int grouped_impl(const icka_gemm_desc* descs, int32_t n, const icka_slab_reduction* reds, int32_t n_red,
-                        hipStream_t st);
+                        hipStream_t st, const uint8_t* const* k_live = nullptr);
 
 extern "C" int icka_gemm_grouped(const icka_gemm_desc* descs, int32_t n, void* stream) {
     if (!descs || n <= 0) return ICKA_E_ARG;
     return grouped_impl(descs, n, nullptr, 0, (hipStream_t)stream);
 }
 
-extern "C" int icka_gemm_grouped_ex(const icka_gemm_desc* descs, int32_t n, const icka_slab_reduction* reds,
-                                    int32_t n_red, void* stream) {
+static int grouped_args_ok(const icka_gemm_desc* descs, int32_t n, const icka_slab_reduction* reds, int32_t n_red) {
     if (n < 0 || n_red < 0 || (n > 0 && !descs) || (n_red > 0 && !reds) || n_red > MAX_RED) return ICKA_E_ARG;
     for (int r = 0; r < n_red; ++r)
         if (!reds[r].partials || reds[r].nslab <= 0 || reds[r].H <= 0 || reds[r].nslots <= 0 || reds[r].nslots > 4 ||
             reds[r].slab_stride < (int64_t)reds[r].nslots * reds[r].H)
             return ICKA_E_ARG;
+    return 0;
+}
+
+extern "C" int icka_gemm_grouped_ex(const icka_gemm_desc* descs, int32_t n, const icka_slab_reduction* reds,
+                                    int32_t n_red, void* stream) {
+    const int rc = grouped_args_ok(descs, n, reds, n_red);
+    if (rc) return rc;
     return grouped_impl(descs, n, reds, n_red, (hipStream_t)stream);
+}
+
+// icka_gemm_grouped_ex with optional row-liveness flags per problem: k_live[i] (NULL allowed) points to K bytes, 16-byte
+// aligned, byte t == 0 only if row t of one of problem i's operands is all zero.  The 12-wave 256x128 launch of TN
+// problems then reduces over the k-tiles that have a live row; every other path ignores the flags and reduces over all
+// of K (skipping is an optimisation, never a requirement).
+extern "C" int icka_gemm_grouped_live(const icka_gemm_desc* descs, int32_t n, const icka_slab_reduction* reds,
+                                      int32_t n_red, const uint8_t* const* k_live, void* stream) {
+    if (k_live)
+        for (int i = 0; i < n; ++i)
+            if (reinterpret_cast<uintptr_t>(k_live[i]) & 15) return ICKA_E_ALIGN;
+    const int rc = grouped_args_ok(descs, n, reds, n_red);
+    if (rc) return rc;
+    return grouped_impl(descs, n, reds, n_red, (hipStream_t)stream, k_live);
 }
 
 static SlabRed to_red(const icka_slab_reduction& r) {
@@ -2675,7 +2792,7 @@ static SlabRed to_red(const icka_slab_reduction& r) {
 }
 
 static int grouped_impl(const icka_gemm_desc* descs, int32_t n, const icka_slab_reduction* reds, int32_t n_red,
-                        hipStream_t st) {
+                        hipStream_t st, const uint8_t* const* k_live) {
     bool reds_done = n_red == 0;
     int i = 0;
     // the group's launch heuristics: the environment default, overridden by the FIRST problem's tune word
@@ -2695,6 +2812,7 @@ static int grouped_impl(const icka_gemm_desc* descs, int32_t n, const icka_slab_
                 if (rc) return rc;
                 if (!big_ok(g, aligned)) break;
                 ba.p[cnt] = g;
+                ba.k_live[cnt] = k_live ? k_live[i + cnt] : nullptr;
                 ba.start[cnt] = total;
                 ba.cs_start[cnt] = cs_total;
                 total += (g.M / 256) * (g.N / BN);
@@ -2703,7 +2821,7 @@ static int grouped_impl(const icka_gemm_desc* descs, int32_t n, const icka_slab_
             }
             if (cnt >= 1 && total >= 64) {
                 for (int k = cnt; k <= MAX_GROUP; ++k) { ba.start[k] = total; ba.cs_start[k] = cs_total; }
-                for (int k = cnt; k < MAX_GROUP; ++k) ba.p[k] = ba.p[0];
+                for (int k = cnt; k < MAX_GROUP; ++k) { ba.p[k] = ba.p[0]; ba.k_live[k] = nullptr; }
                 int red_total = 0;
                 for (int r = 0; r < MAX_RED; ++r) {
                     ba.red_start[r] = red_total;
@@ -2713,9 +2831,16 @@ static int grouped_impl(const icka_gemm_desc* descs, int32_t n, const icka_slab_
                 ba.red_start[MAX_RED] = red_total;
                 reds_done = true;
                 bool wire = false;
-                for (int k = 0; k < cnt; ++k) wire = wire || ba.p[k].C3 != nullptr;
+                bool live = false;   // (a compile-time instance: run-time switches in these bodies cost 5-9 %)
+                for (int k = 0; k < cnt; ++k) {
+                    wire = wire || ba.p[k].C3 != nullptr;
+                    live = live || ba.k_live[k] != nullptr;
+                }
                 const dim3 grid(total + cs_total + red_total);
-                if (t.big == 2) {
+                if (t.big == 2 && live) {
+                    if (wire) hipLaunchKernelGGL((gemm_big_group_kernel<true, true, true>), grid, dim3(768), 0, st, ba);
+                    else hipLaunchKernelGGL((gemm_big_group_kernel<true, false, true>), grid, dim3(768), 0, st, ba);
+                } else if (t.big == 2) {
                     if (wire) hipLaunchKernelGGL((gemm_big_group_kernel<true, true>), grid, dim3(768), 0, st, ba);
                     else hipLaunchKernelGGL((gemm_big_group_kernel<true, false>), grid, dim3(768), 0, st, ba);
                 } else {

@@ -26,7 +26,19 @@ struct LnBwdArgs {
     const bf16_t* dy; int64_t lddy; const bf16_t* dy2; int64_t lddy2; const bf16_t* xhat; const float* rstd;
     const float* gamma; bf16_t* dres; int64_t lddres; bf16_t* dx; int64_t lddx; float* partials;
     int M, H; DropCfg drop;
+    // optional row-liveness bytes for the weight-gradient GEMMs (icka_ln_bwd_slabs_live): row_live[row] = some ds[e] != 0;
+    // row_live_kv[row] = row_live[row] | key ``row`` of the additive mask [M / mask_S, mask_S] can still receive probability
+    uint8_t* row_live; uint8_t* row_live_kv; const float* add_mask; int mask_S;
 };
+
+// A key is closed -- removed from the softmax for good -- when its additive mask value lies this far or further below the
+// mask value of SOME key of its sample: mask[t] - mask[k] <= ICKA_MASKED_KEY_MAX.  It stands for: the backward recomputes
+// P = exp(s + mask - lse) (attn_core.h / attention.hip: __expf of exactly that argument, or a select that gives 0), which
+// is exactly 0 in f32 once the argument is below -104; lse >= s_k + mask[k], so the argument at key t is at most
+// s_t - s_k - 5000, below -104 for every finite score of a sane run.  The rule compares mask values with each other, not
+// with 0, so it is the same for the library's own 0 / -10000 mask, for a graded mask, and for a sample whose keys are ALL
+// at -10000 (lse then sits at the mask value itself, the masked keys do receive probability, and no key is closed).
+constexpr float ICKA_MASKED_KEY_MAX = -5000.f;
 
 // Combine the 4 waves' per-lane column sums through LDS and write this block's slab: partials[blk][slot][H].
 template <int NCH, int NS>
@@ -72,7 +84,9 @@ __device__ __forceinline__ void unpack8(const u32x4 raw, float (&o)[8]) {
     for (int e = 0; e < 8; ++e) o[e] = bf2f(v[e]);
 }
 
-template <int NCH>
+// LIVE: also write the row-liveness bytes (a.row_live, optionally a.row_live_kv); a compile-time instance, so the plain
+// backward keeps its registers and occupancy.
+template <int NCH, bool LIVE = false>
 __device__ __forceinline__ void ln_rows_body(const LnBwdArgs& a_, int blk, int nblk) {
     LnBwdArgs a = a_;
     a.drop = drop_resolve(a.drop);
@@ -85,6 +99,15 @@ __device__ __forceinline__ void ln_rows_body(const LnBwdArgs& a_, int blk, int n
     for (int row = wid; row < a.M; row += nw) {
         float xh[NCH][8], gd[NCH][8];
         float s1 = 0.f, s2 = 0.f;
+        // row_live_kv: the key's own mask value and the first 128 mask values of its sample are only ISSUED here; they are
+        // consumed after the row sums below, when the row's operands (issued earlier) have arrived anyway
+        float m_self = 0.f, m_lo = 0.f, m_hi = 0.f;
+        if (LIVE && a.row_live_kv) {
+            const float* ms = a.add_mask + (int64_t)(row / a.mask_S) * a.mask_S;
+            m_self = a.add_mask[row];
+            m_lo = lane < a.mask_S ? ms[lane] : m_self;      // (lanes past the sample compare the key with itself)
+            m_hi = lane + 64 < a.mask_S ? ms[lane + 64] : m_self;
+        }
         // the keep decisions of the row's dropout mask FIRST (one bit each), while the loads are in flight: left next to
         // their use after the row reductions, the 8 hashes per chunk sat on the critical path of a latency-bound kernel
         // (+1.1 us per launch at 4096 x 768, tools/ln_bench.py)
@@ -126,11 +149,20 @@ __device__ __forceinline__ void ln_rows_body(const LnBwdArgs& a_, int blk, int n
                 }
             }
         }
+        // wave-uniform: no key of the sample lies 5000 or more above this one (see ICKA_MASKED_KEY_MAX)
+        bool key_open = true;
+        if (LIVE && a.row_live_kv) {
+            bool above = m_self - m_lo <= ICKA_MASKED_KEY_MAX || m_self - m_hi <= ICKA_MASKED_KEY_MAX;
+            const float* ms = a.add_mask + (int64_t)(row / a.mask_S) * a.mask_S;
+            for (int k = lane + 128; k < a.mask_S; k += 64) above = above || m_self - ms[k] <= ICKA_MASKED_KEY_MAX;
+            key_open = __ballot(above) == 0;
+        }
         // a wave that owns another row issues its loads now: they are in flight under the reductions and stores below
         const int nrow = row + nw;
         if (nrow < a.M) ln_bwd_load_raw<NCH>(a, nrow, lane, nchunk, rdy, rdy2, rxh);
         const float c1 = wave_sum(s1) * inv_h, c2 = wave_sum(s2) * inv_h;
         const float rstd = a.rstd[row];
+        bool nz = false;   // some element of this lane's part of ds (BEFORE the dropout mask: dres carries ds on) is non-zero
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const int c = lane + 64 * i;
@@ -138,12 +170,23 @@ __device__ __forceinline__ void ln_rows_body(const LnBwdArgs& a_, int blk, int n
                 float ds[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) ds[e] = rstd * (gd[i][e] - c1 - xh[i][e] * c2);
+                if constexpr (LIVE) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) nz = nz || ds[e] != 0.f;
+                }
                 if (a.dres) store8(a.dres + (int64_t)row * a.lddres + c * 8, ds);
                 if (a.drop.thr) {  // gradient of the dense output: through the (re-generated) dropout mask
 #pragma unroll
                     for (int e = 0; e < 8; ++e) ds[e] *= ((kb[i] >> e) & 1u) ? a.drop.scale : 0.f;
                 }
                 if (a.dx) store8(a.dx + (int64_t)row * a.lddx + c * 8, ds);
+            }
+        }
+        if constexpr (LIVE) {   // wave-wide OR, one byte store from lane 0
+            const bool live = __ballot(nz) != 0;
+            if (lane == 0) {
+                a.row_live[row] = live ? 1 : 0;
+                if (a.row_live_kv) a.row_live_kv[row] = (live || key_open) ? 1 : 0;
             }
         }
     }
@@ -222,11 +265,11 @@ __global__ __launch_bounds__(256) void ln_cols_kernel(const bf16_t* __restrict__
 struct LnColsArgs {
     int nx, groups, rows_per_group;
 };
-template <int NCH>
+template <int NCH, bool LIVE = false>
 __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(const LnBwdArgs a, const LnColsArgs c) {
     const int ncol = c.nx * c.groups;
     if ((int)blockIdx.x >= ncol) {
-        ln_rows_body<NCH>(a, blockIdx.x - ncol, gridDim.x - ncol);
+        ln_rows_body<NCH, LIVE>(a, blockIdx.x - ncol, gridDim.x - ncol);
         return;
     }
     ln_cols_body(a.dy, a.lddy, a.dy2, a.lddy2, a.xhat, nullptr, 0, a.partials, a.M, a.H, c.rows_per_group,
@@ -660,22 +703,34 @@ extern "C" int32_t icka_ln_bwd_nslab(int32_t M) {
 }
 extern "C" int32_t icka_ln_slab_slots(void) { return SLOTS; }
 
-extern "C" int icka_ln_bwd_slabs(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* xhat,
-                                 const float* rstd, const float* gamma, void* dres, int64_t lddres, void* dx,
-                                 int64_t lddx, float* partials, int32_t M, int32_t H, float p_drop, uint64_t seed,
-                                 void* stream) {
+static int ln_bwd_slabs_impl(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* xhat,
+                             const float* rstd, const float* gamma, void* dres, int64_t lddres, void* dx,
+                             int64_t lddx, float* partials, int32_t M, int32_t H, float p_drop, uint64_t seed,
+                             uint8_t* row_live, uint8_t* row_live_kv, const float* add_mask, int32_t mask_S,
+                             void* stream) {
     if (!dy || !xhat || !rstd || !gamma || !partials) return ICKA_E_ARG;
     if (M <= 0 || H <= 0 || H % 8 != 0 || H > 8 * 64 * MAX_CH) return ICKA_E_SHAPE;
     if (lddy % 8 || (dy2 && lddy2 % 8) || (dres && lddres % 8) || (dx && lddx % 8)) return ICKA_E_ALIGN;
     if (!al16(dy) || (dy2 && !al16(dy2)) || !al16(xhat) || (dres && !al16(dres)) || (dx && !al16(dx)) || !al16(gamma))
         return ICKA_E_ALIGN;
     LnBwdArgs a{(const bf16_t*)dy, lddy, (const bf16_t*)dy2, lddy2, (const bf16_t*)xhat, rstd, gamma,
-                (bf16_t*)dres, lddres, (bf16_t*)dx, lddx, partials, M, H, make_drop(p_drop, seed)};
+                (bf16_t*)dres, lddres, (bf16_t*)dx, lddx, partials, M, H, make_drop(p_drop, seed),
+                row_live, row_live_kv, add_mask, mask_S};
     const int groups = icka_ln_bwd_nslab(M);
     const int nx = (H + 255) / 256;
     const LnColsArgs c{nx, groups, (M + groups - 1) / groups};
     const int grid = nx * groups + bwd_row_grid(M);
     hipStream_t st = (hipStream_t)stream;
+    if (row_live) {
+        switch (pick_nch(H)) {
+            case 1: hipLaunchKernelGGL((ln_bwd_fused_kernel<1, true>), dim3(grid), dim3(256), 0, st, a, c); break;
+            case 2: hipLaunchKernelGGL((ln_bwd_fused_kernel<2, true>), dim3(grid), dim3(256), 0, st, a, c); break;
+            case 3: hipLaunchKernelGGL((ln_bwd_fused_kernel<3, true>), dim3(grid), dim3(256), 0, st, a, c); break;
+            default: hipLaunchKernelGGL((ln_bwd_fused_kernel<4, true>), dim3(grid), dim3(256), 0, st, a, c); break;
+        }
+        ICKA_CHECK_LAUNCH();
+        return 0;
+    }
     switch (pick_nch(H)) {
         case 1: hipLaunchKernelGGL((ln_bwd_fused_kernel<1>), dim3(grid), dim3(256), 0, st, a, c); break;
         case 2: hipLaunchKernelGGL((ln_bwd_fused_kernel<2>), dim3(grid), dim3(256), 0, st, a, c); break;
@@ -684,6 +739,27 @@ extern "C" int icka_ln_bwd_slabs(const void* dy, int64_t lddy, const void* dy2, 
     }
     ICKA_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int icka_ln_bwd_slabs(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* xhat,
+                                 const float* rstd, const float* gamma, void* dres, int64_t lddres, void* dx,
+                                 int64_t lddx, float* partials, int32_t M, int32_t H, float p_drop, uint64_t seed,
+                                 void* stream) {
+    return ln_bwd_slabs_impl(dy, lddy, dy2, lddy2, xhat, rstd, gamma, dres, lddres, dx, lddx, partials, M, H, p_drop, seed,
+                             nullptr, nullptr, nullptr, 0, stream);
+}
+
+// icka_ln_bwd_slabs + the row-liveness bytes of the rows it just produced (u8 [M] each).  row_live_kv is optional and
+// needs the additive key mask add_mask (f32 [M / mask_S, mask_S], M % mask_S == 0): see ICKA_MASKED_KEY_MAX.
+extern "C" int icka_ln_bwd_slabs_live(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* xhat,
+                                      const float* rstd, const float* gamma, void* dres, int64_t lddres, void* dx,
+                                      int64_t lddx, float* partials, uint8_t* row_live, uint8_t* row_live_kv,
+                                      const float* add_mask, int32_t mask_S, int32_t M, int32_t H, float p_drop,
+                                      uint64_t seed, void* stream) {
+    if (!row_live) return ICKA_E_ARG;
+    if (row_live_kv && (!add_mask || mask_S <= 0 || M % mask_S != 0)) return ICKA_E_ARG;
+    return ln_bwd_slabs_impl(dy, lddy, dy2, lddy2, xhat, rstd, gamma, dres, lddres, dx, lddx, partials, M, H, p_drop, seed,
+                             row_live, row_live_kv, row_live_kv ? add_mask : nullptr, mask_S, stream);
 }
 
 static int embed_fwd_impl(int32_t twin_f16, const int64_t* ids, const int64_t* token_type, const float* word, const float* pos,

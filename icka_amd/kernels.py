@@ -316,9 +316,11 @@ def cls_head_bwd(dl, seq, gated, gate, cross, W, dseq, du, dcross, partials):
     return lib.icka_cls_head_bwd_slabs(M)
 
 
-def gemm_grouped(descs, reductions=None) -> None:
+def gemm_grouped(descs, reductions=None, k_live=None) -> None:
     """Launch several GEMMs (gemm_desc results) at once; same-layout fast-path problems share one launch.
-    ``reductions``: slab_reduction descriptors (at most 4) summed by extra blocks of the same launch."""
+    ``reductions``: slab_reduction descriptors (at most 4) summed by extra blocks of the same launch.
+    ``k_live``: per problem None or a uint8 [K] tensor of row-liveness flags (icka_gemm_grouped_live): byte t may be 0 only
+    if row t of one of the problem's operands is all zero; the 12-wave weight-gradient launch then skips dead k-tiles."""
     reductions = reductions or []
     if not descs and not reductions:
         return
@@ -326,6 +328,17 @@ def gemm_grouped(descs, reductions=None) -> None:
     arr = (GemmDesc * max(len(descs), 1))(*descs)
     if _PROF is not None and descs:
         _PROF.append((1, arr, len(descs), list(descs)))
+    if k_live is not None and any(f is not None for f in k_live):
+        if len(k_live) != len(descs) or len(reductions) > 4:
+            raise ValueError("gemm_grouped: one k_live entry per problem, at most 4 reductions")
+        for f, dsc in zip(k_live, descs):
+            if f is not None and (f.dtype != torch.uint8 or not f.is_contiguous() or f.numel() != dsc.K):
+                raise ValueError("gemm_grouped: k_live must be a contiguous uint8 [K] tensor")
+        larr = (C.c_void_p * len(descs))(*[None if f is None else f.data_ptr() for f in k_live])
+        rarr = (_lib.SlabReduction * max(len(reductions), 1))(*reductions)
+        check(lib.icka_gemm_grouped_live(arr, len(descs), rarr if reductions else None, len(reductions), larr, _stream()),
+              "icka_gemm_grouped_live")
+        return
     if not reductions:
         check(lib.icka_gemm_grouped(arr, len(descs), _stream()), "icka_gemm_grouped")
         return
@@ -476,6 +489,29 @@ def ln_bwd_slabs(dy, xhat, rstd, gamma, partials, *, dy2=None, dres=None, dx=Non
     check(lib.icka_ln_bwd_slabs(dy.data_ptr(), dy.stride(0), _ptr(dy2), _ld(dy2), xhat.data_ptr(), rstd.data_ptr(),
                                 gamma.data_ptr(), _ptr(dres), _ld(dres), _ptr(dx), _ld(dx), partials.data_ptr(), M, H,
                                 p_drop, seed, _stream()), "icka_ln_bwd_slabs")
+    return lib.icka_ln_bwd_nslab(M)
+
+
+def ln_bwd_slabs_live(dy, xhat, rstd, gamma, partials, row_live, *, row_live_kv=None, add_mask=None, dy2=None, dres=None,
+                      dx=None, p_drop=0.0, seed=0) -> int:
+    """ln_bwd_slabs that also writes the row-liveness bytes (uint8 [M]) of the gradient rows it produced: ``row_live`` (some
+    element of dres is non-zero) and optionally ``row_live_kv`` (... or the row is a key the additive mask f32 [B,S] leaves
+    open): the k_live flags of the weight gradients downstream (gemm_grouped)."""
+    lib = _lib.load()
+    _mat(dy, "dy"); _mat(xhat, "xhat")
+    M, H = dy.shape
+    for f in (row_live, row_live_kv):
+        if f is not None and (f.dtype != torch.uint8 or not f.is_contiguous() or f.numel() != M):
+            raise ValueError("ln_bwd_slabs_live: the flags are contiguous uint8 [M] tensors")
+    S = 0
+    if row_live_kv is not None:
+        if add_mask is None or add_mask.dtype != F32 or not add_mask.is_contiguous() or add_mask.numel() != M:
+            raise ValueError("ln_bwd_slabs_live: row_live_kv needs the contiguous f32 additive mask [B,S] with B*S == M")
+        S = add_mask.shape[-1]
+    check(lib.icka_ln_bwd_slabs_live(dy.data_ptr(), dy.stride(0), _ptr(dy2), _ld(dy2), xhat.data_ptr(), rstd.data_ptr(),
+                                     gamma.data_ptr(), _ptr(dres), _ld(dres), _ptr(dx), _ld(dx), partials.data_ptr(),
+                                     row_live.data_ptr(), _ptr(row_live_kv), _ptr(add_mask) if S else None, S, M, H,
+                                     p_drop, seed, _stream()), "icka_ln_bwd_slabs_live")
     return lib.icka_ln_bwd_nslab(M)
 
 

@@ -37,6 +37,10 @@ FUSE_DENSE_LN_MIN_ROWS = 3072
 # bitwise the two launches).  "0" keeps the two launches.  The library itself declines grids below 128 tiles.
 FUSE_QKV_ATTN = _os.environ.get("ICKA_FUSE_QKV_ATTN", "1") != "0"
 FUSE_QKV_ATTN_MIN_ROWS = 3072
+# The weight gradients of a BERT layer reduce over the token rows whose gradient is non-zero only: the LayerNorm backward leaves one
+# liveness byte per row and the 12-wave weight-gradient launch skips the 64-token k-tiles without a live row (padding, when the
+# caller's loss leaves it without gradient).  Bitwise the full reduction.  "0" reduces over every row (same-box A/B: tools/ab_env.sh).
+WGRAD_LIVE = _os.environ.get("ICKA_WGRAD_LIVE", "1") != "0"
 
 
 def _keepbits_on(Sq: int, Skv: int) -> bool:
@@ -89,9 +93,10 @@ def _fwd_twin(A: ParamArena, x, xf, d: Dims):
 # Weight gradients (dW = dY^T . X, reduction over the tokens) have no consumer inside backward: each block queues
 # them and launches the whole batch as ONE grouped GEMM at the end of its backward (4 GEMMs of 36..144 tiles each
 # fill the 256 CUs together instead of one after the other).
-def _wgrad(A: ParamArena, dy, x, gout, beta: float, bias=None) -> None:
+def _wgrad(A: ParamArena, dy, x, gout, beta: float, bias=None, k_live=None) -> None:
     """Queue dW (+)= dy^T . x; with ``bias`` (parameter or tuple of adjacent parameters) also db (+)= colsum(dy),
-    fused into the same GEMM when the shape is on the fast path, else by the column-sum kernel."""
+    fused into the same GEMM when the shape is on the fast path, else by the column-sum kernel.  ``k_live``: uint8 [tokens]
+    row-liveness flags of ``dy`` (byte t == 0 only if row t of dy is all zero), see the note above _ln_bwd_deferred."""
     bout, bacc = None, False
     if bias is not None:
         bacc = A.grad_beta(bias) > 0
@@ -104,26 +109,53 @@ def _wgrad(A: ParamArena, dy, x, gout, beta: float, bias=None) -> None:
     # data parallel with bf16 buckets: the same epilogue writes the bf16 wire copy of the gradient (ParamArena.wire_of)
     wire = A.wire_of(gout, beta)
     A.pending_wgrad.append((K.gemm_desc(K.GEMM_TN, dy, x, gout, beta=beta, colsum_out=bout, colsum_accumulate=bacc,
-                                        **wire), dy, x, gout, bout, wire))
+                                        **wire), dy, x, gout, bout, wire, k_live))
 
 
 def _flush_wgrad(A: ParamArena) -> None:
     """One grouped launch for the block's queued weight gradients; the LayerNorm dgamma / dbeta slab reductions queued
     by _ln_bwd_deferred are summed by extra blocks of the same launch."""
     if A.pending_wgrad or A.pending_reductions:
-        K.gemm_grouped([t[0] for t in A.pending_wgrad], reductions=A.pending_reductions)
+        flags = [t[6] for t in A.pending_wgrad]
+        if any(f is not None for f in flags):
+            K.gemm_grouped([t[0] for t in A.pending_wgrad], reductions=A.pending_reductions, k_live=flags)
+        else:
+            K.gemm_grouped([t[0] for t in A.pending_wgrad], reductions=A.pending_reductions)
         A.pending_wgrad = []
         A.pending_reductions = []
 
 
-def _ln_bwd_deferred(A: ParamArena, tag: str, norm, dy, xhat, rstd, *, dy2, dres, dx, p_drop, seed) -> None:
+# Row-liveness flags of the weight gradients (WGRAD_LIVE; BertLayerFn.backward only).  The decision comes from the gradient DATA,
+# never from the padding mask alone: the caller owns the loss and may put gradient on masked rows.  The LayerNorm backward of a
+# sub-block holds a whole row of ds (the residual gradient before the dropout mask) in one wave and writes row_live[t] = any(ds_t != 0).
+# Why a dead row is an all-zero row of every weight-gradient operand downstream:
+#   * dfo / dao (the dense-output gradients) are ds times the dropout mask: zero wherever ds is.
+#   * dz = (dfo . W2^T) o gelu'(z): a zero row in gives a zero row out (0 * finite sums to 0 in the f32 accumulator).
+#   * dqkv row t: the query part is zero because dctx_t = dao_t . Wo = 0; the key and value parts are zero because every query's
+#     P at key t is exactly 0 once the additive mask removes the key (row_live_kv: see ICKA_MASKED_KEY_MAX in csrc/layernorm.hip).
+# For each skipped k-tile the full kernel adds only +-0 products to an accumulator that started at +0, so the results are bitwise
+# those of the full reduction whenever the activations X are finite (with Inf / NaN there the full reduction gives NaN, the
+# shortened one may not).
+def _ln_bwd_deferred(A: ParamArena, tag: str, norm, dy, xhat, rstd, *, dy2, dres, dx, p_drop, seed, live=False, add_mask=None):
     """LayerNorm backward of a block: rows now, the parameter-gradient finalize with the block's weight-gradient launch
-    (saves one launch per LayerNorm).  ``tag`` keeps the slab workspaces of one block apart."""
+    (saves one launch per LayerNorm).  ``tag`` keeps the slab workspaces of one block apart.
+    ``live``: also write the row-liveness flags; returns (row_live, row_live_kv or None) -- row_live_kv with ``add_mask``
+    (f32 [B,S]) -- else None."""
     H = dy.shape[1]
     ws = A.workspace(tag, K._lib.load().icka_ln_bwd_workspace_floats(H))
     acc = A.grad_beta((norm.weight, norm.bias)) > 0
-    nslab = K.ln_bwd_slabs(dy, xhat, rstd, norm.weight, ws, dy2=dy2, dres=dres, dx=dx, p_drop=p_drop, seed=seed)
+    flags = None
+    if live:
+        # (allocated like dres / dx: static addresses under graph capture)
+        row_live = _empty(dy, dy.shape[0], dtype=torch.uint8)
+        row_live_kv = _empty(dy, dy.shape[0], dtype=torch.uint8) if add_mask is not None else None
+        nslab = K.ln_bwd_slabs_live(dy, xhat, rstd, norm.weight, ws, row_live, row_live_kv=row_live_kv, add_mask=add_mask,
+                                    dy2=dy2, dres=dres, dx=dx, p_drop=p_drop, seed=seed)
+        flags = (row_live, row_live_kv)
+    else:
+        nslab = K.ln_bwd_slabs(dy, xhat, rstd, norm.weight, ws, dy2=dy2, dres=dres, dx=dx, p_drop=p_drop, seed=seed)
     A.pending_reductions.append(K.slab_reduction(ws, nslab, H, (A.g(norm.weight), A.g(norm.bias)), acc))
+    return flags
 
 
 # =============================================================================================== sub-blocks
@@ -265,8 +297,10 @@ def _attn_core_fwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
     return ctx, ctx16, ((qkv, kvbuf, lse, seed_a, kb) if save else None)
 
 
-def _attn_core_bwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, saved, ctx, dctx, dres, need_dkv_src: bool):
-    """Returns (dx, dkv_src); ``dres`` (optional) is added to dx in the last GEMM's epilogue (residual fan-in)."""
+def _attn_core_bwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, saved, ctx, dctx, dres, need_dkv_src: bool,
+                   k_live=None):
+    """Returns (dx, dkv_src); ``dres`` (optional) is added to dx in the last GEMM's epilogue (residual fan-in).
+    ``k_live`` (self-attention only): row-liveness flags of dqkv (row_live_kv of the block's LayerNorm backward)."""
     qkv, kvbuf, lse, seed_a, kb = saved
     M, H = x.shape
     generic = isinstance(lse, tuple)       # head size != 64: the saved f32 operands / probabilities of _attn_generic_fwd
@@ -285,7 +319,7 @@ def _attn_core_bwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
                        d.heads, d.S, Skv, p_drop=d.p_attn, seed=seed_a, keepbits=kb)
         wg = (sa.query.weight, sa.key.weight, sa.value.weight)
         bg = (sa.query.bias, sa.key.bias, sa.value.bias)
-        _wgrad(A, dqkv, x, A.g_cat(wg), A.grad_beta(wg), bias=bg)
+        _wgrad(A, dqkv, x, A.g_cat(wg), A.grad_beta(wg), bias=bg, k_live=k_live)
         dx = _empty(x, M, H)
         K.gemm(K.GEMM_NN, dqkv, A.w_cat(wg), dx, **epi)
         return dx, None
@@ -345,18 +379,21 @@ def _dense_norm_fwd(A: ParamArena, mod, h, res, d: Dims, save: bool, h16=None):
     return y, yf, ((xhat, rstd, seed_h) if save else None)
 
 
-def _dense_norm_bwd(A: ParamArena, tag: str, mod, h, d: Dims, saved, dy, dy2):
-    """Returns (do, dres): gradient of the dense OUTPUT (dropout mask applied; the caller turns it into the gradient of
-    ``h`` with the epilogue it wants) and of the residual input.  Queues dW / db (_wgrad) and the LayerNorm parameter
-    reduction; the caller flushes."""
+def _dense_norm_bwd(A: ParamArena, tag: str, mod, h, d: Dims, saved, dy, dy2, live=False, add_mask=None):
+    """Returns (do, dres, flags): gradient of the dense OUTPUT (dropout mask applied; the caller turns it into the gradient
+    of ``h`` with the epilogue it wants) and of the residual input; ``flags`` is None, or with ``live`` the row-liveness flags
+    (row_live, row_live_kv or None) of _ln_bwd_deferred.  Queues dW / db (_wgrad) and the LayerNorm parameter reduction; the
+    caller flushes."""
     xhat, rstd, seed_h = saved
     M, H = xhat.shape
     dres = _empty(h, M, H)
     do = _empty(h, M, H)
-    _ln_bwd_deferred(A, tag, mod.LayerNorm, dy, xhat, rstd, dy2=dy2, dres=dres, dx=do, p_drop=d.p_hidden, seed=seed_h)
+    flags = _ln_bwd_deferred(A, tag, mod.LayerNorm, dy, xhat, rstd, dy2=dy2, dres=dres, dx=do, p_drop=d.p_hidden, seed=seed_h,
+                             live=live, add_mask=add_mask)
     # the dense bias gradient (column sums of do) rides on the weight-gradient GEMM
-    _wgrad(A, do, h, A.g(mod.dense.weight), A.grad_beta(mod.dense.weight), bias=mod.dense.bias)
-    return do, dres
+    _wgrad(A, do, h, A.g(mod.dense.weight), A.grad_beta(mod.dense.weight), bias=mod.dense.bias,
+           k_live=flags[0] if flags else None)
+    return do, dres, flags
 
 
 def _inter_fwd(A: ParamArena, inter, x, x16=None):
@@ -375,9 +412,9 @@ def _inter_fwd(A: ParamArena, inter, x, x16=None):
     return g, z, None
 
 
-def _inter_bwd(A: ParamArena, inter, x, dz, dres):
+def _inter_bwd(A: ParamArena, inter, x, dz, dres, k_live=None):
     """dz = gradient of the pre-activation.  Returns dx (+ dres when given)."""
-    _wgrad(A, dz, x, A.g(inter.dense.weight), A.grad_beta(inter.dense.weight), bias=inter.dense.bias)
+    _wgrad(A, dz, x, A.g(inter.dense.weight), A.grad_beta(inter.dense.weight), bias=inter.dense.bias, k_live=k_live)
     dx = _empty(x, x.shape[0], x.shape[1])
     if dres is not None:
         K.gemm(K.GEMM_NN, dz, A.w(inter.dense.weight), dx, epilogue=K.EPI_ADD, aux=dres)
@@ -398,13 +435,18 @@ def _attn_block_fwd(A: ParamArena, att, x, xres, kv_src, add_mask, d: Dims, Skv:
     return y, yf, ((ctx, s_core, s_out) if save else None)
 
 
-def _attn_block_bwd(A: ParamArena, att, x, kv_src, add_mask, d: Dims, Skv: int, saved, dy, dy2, need_dkv_src: bool):
-    """Returns (dx, dkv_src).  dy2 is an optional second gradient of the block output (fused into the LN backward)."""
+def _attn_block_bwd(A: ParamArena, att, x, kv_src, add_mask, d: Dims, Skv: int, saved, dy, dy2, need_dkv_src: bool,
+                    live=False):
+    """Returns (dx, dkv_src).  dy2 is an optional second gradient of the block output (fused into the LN backward).
+    ``live`` (self-attention): the weight gradients of the block reduce over live rows only."""
     ctx, s_core, s_out = saved
-    dao, dres = _dense_norm_bwd(A, "ln_attn", att.output, ctx, d, s_out, dy, dy2)
+    live = live and kv_src is None
+    dao, dres, flags = _dense_norm_bwd(A, "ln_attn", att.output, ctx, d, s_out, dy, dy2, live=live,
+                                       add_mask=add_mask if live else None)
     dctx = _empty(x, x.shape[0], x.shape[1])
     K.gemm(K.GEMM_NN, dao, A.w(att.output.dense.weight), dctx)
-    return _attn_core_bwd(A, att.self, x, kv_src, add_mask, d, Skv, s_core, ctx, dctx, dres, need_dkv_src)
+    return _attn_core_bwd(A, att.self, x, kv_src, add_mask, d, Skv, s_core, ctx, dctx, dres, need_dkv_src,
+                          k_live=flags[1] if flags else None)
 
 
 def _ffn_block_fwd(A: ParamArena, layer, x, xres, d: Dims, save: bool):
@@ -415,13 +457,13 @@ def _ffn_block_fwd(A: ParamArena, layer, x, xres, d: Dims, save: bool):
     return y, yf, ((z, g, s_out) if save else None)
 
 
-def _ffn_block_bwd(A: ParamArena, layer, x, d: Dims, saved, dy, dy2=None):
+def _ffn_block_bwd(A: ParamArena, layer, x, d: Dims, saved, dy, dy2=None, live=False):
     """Returns the gradient of the block input: through the dense path (dz @ W1) WITH the residual gradient added."""
     z, g, s_out = saved
-    dfo, dres = _dense_norm_bwd(A, "ln_ffn", layer.output, g, d, s_out, dy, dy2)
+    dfo, dres, flags = _dense_norm_bwd(A, "ln_ffn", layer.output, g, d, s_out, dy, dy2, live=live)
     dz = _empty(x, z.shape[0], z.shape[1])
     K.gemm(K.GEMM_NN, dfo, A.w(layer.output.dense.weight), dz, epilogue=K.EPI_DGELU, aux=z)
-    return _inter_bwd(A, layer.intermediate, x, dz, dres)
+    return _inter_bwd(A, layer.intermediate, x, dz, dres, k_live=flags[0] if flags else None)
 
 
 # =============================================================================================== Functions
@@ -498,8 +540,10 @@ class BertLayerFn(torch.autograd.Function):
     def backward(ctx, dy, _dyf=None):
         x, x1, add_mask = ctx.saved_tensors
         layer, A, d = ctx.layer, ctx.A, ctx.d
-        dx1 = _ffn_block_bwd(A, layer, x1, d, ctx.s_ffn, _c(dy))
-        dx, _ = _attn_block_bwd(A, layer.attention, x, None, add_mask, d, d.S, ctx.s_att, dx1, None, False)
+        # (the flags need one mask value per row: not the packed batches, whose rows are not [B, S])
+        live = WGRAD_LIVE and d.pack is None and add_mask.numel() == x.shape[0]
+        dx1 = _ffn_block_bwd(A, layer, x1, d, ctx.s_ffn, _c(dy), live=live)
+        dx, _ = _attn_block_bwd(A, layer.attention, x, None, add_mask, d, d.S, ctx.s_att, dx1, None, False, live=live)
         if not A.keep_saved:
             ctx.s_att = ctx.s_ffn = None
         _flush_wgrad(A)
@@ -579,7 +623,7 @@ class DenseResidualNormFn(torch.autograd.Function):
     def backward(ctx, dy, _dyf=None):
         (h,) = ctx.saved_tensors
         mod, A = ctx.mod, ctx.A
-        do, dres = _dense_norm_bwd(A, "ln_sub", mod, h, ctx.d, ctx.saved, _c(dy), None)
+        do, dres, _ = _dense_norm_bwd(A, "ln_sub", mod, h, ctx.d, ctx.saved, _c(dy), None)
         dh = torch.empty_like(h)
         K.gemm(K.GEMM_NN, do, A.w(mod.dense.weight), dh)
         if not A.keep_saved:

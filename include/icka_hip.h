@@ -152,6 +152,15 @@ typedef struct icka_slab_reduction {
 } icka_slab_reduction;
 int icka_gemm_grouped_ex(const icka_gemm_desc* descs, int32_t n, const icka_slab_reduction* reds, int32_t n_red,
                          void* stream);
+/* Same, plus optional row-liveness flags per problem: k_live (NULL, or n pointers, each NULL or K bytes, 16-byte
+ * aligned) -- byte t of k_live[i] may be 0 only if row t of one of problem i's two operands is all zero (the weight
+ * gradients: a token whose output gradient is zero; icka_ln_bwd_slabs_live writes such bytes).  The 12-wave 256x128
+ * launch of TN problems then reduces over the 64-row k-tiles that have a live row; the result is bitwise the full
+ * reduction whenever the other operand is finite (a skipped tile only adds +-0 to accumulators that started at +0;
+ * with Inf / NaN there the full reduction gives NaN and the shortened one may not).  Every other path ignores the
+ * flags and reduces over all of K.  The column sums and slab reductions of the launch are not affected. */
+int icka_gemm_grouped_live(const icka_gemm_desc* descs, int32_t n, const icka_slab_reduction* reds, int32_t n_red,
+                           const uint8_t* const* k_live, void* stream);
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused  y = LayerNorm(dropout(x + bias) + residual)   (BertSelfOutput.forward :561-565, BertOutput.forward
  * :532-536, BertLayerNorm.forward :518-522: biased variance, eps inside the sqrt).  One wave per row.
@@ -228,6 +237,16 @@ int icka_ln_bwd(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, co
 int icka_ln_bwd_slabs(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* xhat, const float* rstd,
                       const float* gamma, void* dres, int64_t lddres, void* dx, int64_t lddx, float* partials, int32_t M,
                       int32_t H, float p_drop, uint64_t seed, void* stream);
+/* icka_ln_bwd_slabs + row-liveness bytes of the rows it produced: row_live[row] (u8 [M], required) = 1 if any element
+ * of the row's residual gradient (dres, BEFORE the dropout mask of dx) is non-zero, else 0 -- dx == 0 follows.
+ * row_live_kv (u8 [M], optional; needs the additive key mask add_mask f32 [M / mask_S, mask_S]) additionally keeps a row
+ * live while it can receive attention probability as a KEY: no key of its sample has a mask value 5000 or more
+ * above its own (mask values are compared with each other, not with 0: exact for graded masks and for a sample whose
+ * keys are all masked).  dres / dx / partials are bitwise those of icka_ln_bwd_slabs. */
+int icka_ln_bwd_slabs_live(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* xhat,
+                           const float* rstd, const float* gamma, void* dres, int64_t lddres, void* dx, int64_t lddx,
+                           float* partials, uint8_t* row_live, uint8_t* row_live_kv, const float* add_mask,
+                           int32_t mask_S, int32_t M, int32_t H, float p_drop, uint64_t seed, void* stream);
 int32_t icka_ln_bwd_nslab(int32_t M);
 int32_t icka_ln_slab_slots(void);
 
