@@ -16,6 +16,7 @@ from .modeling import MTCCMBertForMMTokenClassificationCRF_gate_1
 from .dp import GradReducer
 from . import graph
 from .graph import DevicePrefetcher, GraphedModule, GraphedStep
+from .train_step import TrainStep
 from . import cross_modal
 from .cross_modal import PromptRobertaModel
 from . import packing
@@ -28,5 +29,5 @@ __all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "Bert
            "BertSelfAttention", "BertCoAttention", "BertSelfOutput", "BertIntermediate", "BertOutput",
            "BertPreTrainedModel", "MTCCMBertForMMTokenClassificationCRF", "cls_layer_both", "scalar_gate_fusion",
            "token_ce_loss", "set_precision", "resolved_precision", "ParamArena", "cross_modal", "PromptRobertaModel",
-           "GradReducer", "graph", "DevicePrefetcher", "GraphedModule", "GraphedStep", "packing", "set_packed",
+           "GradReducer", "graph", "DevicePrefetcher", "GraphedModule", "GraphedStep", "TrainStep", "packing", "set_packed",
            "PackOverflowError", "TokenBudgetBatchSampler", "metrics", "ChunkEvaluator"]

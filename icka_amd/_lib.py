@@ -59,6 +59,27 @@ class XGemmDesc(C.Structure):
     ]
 
 
+OPTIM_MAX_GROUPS = 8
+OPTIM_SCHEDULE_CONSTANT, OPTIM_SCHEDULE_LINEAR = 0, 1
+OPTIM_DRY, OPTIM_NO_GUARD = 1, 2                          # flags of icka_optim_prepare
+
+
+class OptimState(C.Structure):
+    """Mirror of ``icka_optim_state`` (include/icka_hip.h): the device block of the capturable parameter update.  Bytes
+    [0, HOST_LO) and [HOST_HI, size) are written by icka_optim_prepare, [HOST_LO, HOST_HI) by the host."""
+    _fields_ = [
+        ("t", c_i64), ("skipped", c_i64), ("norm", c_f32), ("coef", c_f32), ("skip", c_i32), ("reserved", c_i32),
+        ("kind", c_i32), ("n_groups", c_i32), ("warmup", c_i64), ("total", c_i64),
+        ("base_lr", C.c_double * OPTIM_MAX_GROUPS),
+        ("beta1", c_f32 * OPTIM_MAX_GROUPS), ("beta2", c_f32 * OPTIM_MAX_GROUPS), ("eps", c_f32 * OPTIM_MAX_GROUPS),
+        ("weight_decay", c_f32 * OPTIM_MAX_GROUPS),
+        ("lr", c_f32 * OPTIM_MAX_GROUPS), ("bc1", c_f32 * OPTIM_MAX_GROUPS), ("bc2_sqrt", c_f32 * OPTIM_MAX_GROUPS),
+    ]
+
+
+OptimState.HOST_LO, OptimState.HOST_HI = OptimState.kind.offset, OptimState.lr.offset
+
+
 # name -> (restype, argtypes); must list every function declared in include/icka_hip.h
 PROTOTYPES = {
     "icka_abi_version": (c_i32, []),
@@ -206,6 +227,8 @@ PROTOTYPES = {
     "icka_optim_clip": (c_i32, [c_vp, c_i32, c_f32, c_vp, c_vp]),
     "icka_optim_adamw": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32,
                                  c_i32, c_vp]),
+    "icka_optim_prepare": (c_i32, [c_vp, c_i32, c_f32, c_i32, c_vp, c_vp]),
+    "icka_optim_adamw_dev": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     # ---- fp32 "exact" mode (csrc/exact.hip)
     "icka_x_gemm": (c_i32, [C.POINTER(XGemmDesc), c_vp]),
     "icka_x_ln_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_u64,

@@ -27,7 +27,8 @@ What the reference's loop does around a step (My_cross_attention.py:797-875) and
     The 1 / k of the loss (:821-822) stays in the caller's ``step_fn``, as in the reference.
   * ``p.grad`` is re-attached to the arena views after every replay (a replay runs no Python), so ``clip_grad_norm_``,
     ``optimizer.step()`` and ``scheduler.step()`` (:841-843) see this cycle's gradients.
-  * The optimizer runs outside the graph.  With the default shadow policy ("always") the bf16 re-cast of the parameters is
+  * The optimizer runs outside the graphs of this module (``train_step.TrainStep`` captures the update of a capturable
+    ``optim.ArenaAdamW`` behind the last micro-batch of a cycle).  With the default shadow policy ("always") the bf16 re-cast of the parameters is
     the first kernel inside the captured forward; with "tracked" it runs before the replay when a change was seen.
   * ``close()`` (also run by ``__del__``) unregisters the dropout nonce, whose device memory the wrapper owns.
 

@@ -1294,6 +1294,67 @@ def dp_check_error(where: str = "") -> None:
                           "an optimizer step that consumed them produced NaN" % ((" (" + where + ")") if where else ""))
 
 
+# ------------------------------------------------------------------------------------------------- capturable parameter update
+def optim_state_new(device) -> torch.Tensor:
+    """A zeroed ``icka_optim_state`` block (include/icka_hip.h; mirror: _lib.OptimState) as a uint8 device tensor."""
+    n = C.sizeof(_lib.OptimState)
+    return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device).view(torch.uint8)[:n]
+
+
+def optim_state_write(state: torch.Tensor, host: "_lib.OptimState", lo: int, hi: int) -> None:
+    """Upload bytes [lo, hi) of ``host`` into the device block (outside a capture: a host-to-device copy)."""
+    state[lo:hi].copy_(torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8)[lo:hi])
+
+
+def optim_state_read(state: torch.Tensor) -> "_lib.OptimState":
+    """The device block as a host structure (one device-to-host copy: synchronises)."""
+    return _lib.OptimState.from_buffer_copy(bytes(state.cpu().tolist()))
+
+
+def optim_chunk_table3(ranges_per_group, device) -> torch.Tensor:
+    """Chunk table of icka_optim_adamw_dev: per group a list of [(lo, hi)] element ranges (multiples of 8) -> int64 [n, 3]
+    device tensor of (first element, count <= icka_optim_chunk_elems(), group)."""
+    if len(ranges_per_group) > _lib.OPTIM_MAX_GROUPS:
+        raise ValueError("at most %d parameter groups" % _lib.OPTIM_MAX_GROUPS)
+    ch = _lib.load().icka_optim_chunk_elems()
+    rows = []
+    for gi, ranges in enumerate(ranges_per_group):
+        for lo, hi in ranges:
+            if lo % 8 or hi % 8:
+                raise ValueError("chunk ranges must start and end on multiples of 8 elements")
+            while lo < hi:
+                n = min(ch, hi - lo)
+                rows.append((lo, n, gi))
+                lo += n
+    return torch.tensor(rows, dtype=torch.int64, device=device).reshape(-1, 3)
+
+
+def optim_sqnorm(gflat: torch.Tensor, table: torch.Tensor, partials: torch.Tensor) -> None:
+    check(_lib.load().icka_optim_sqnorm(gflat.data_ptr(), table.data_ptr(), table.shape[0], partials.data_ptr(), _stream()),
+          "icka_optim_sqnorm")
+
+
+def optim_prepare(partials: Optional[torch.Tensor], n: int, max_norm: float, state: torch.Tensor, dry: bool = False,
+                  guard: bool = True) -> None:
+    """Norm, non-finite test, clip coefficient and the values of the next update into the state block; advances t."""
+    flags = (_lib.OPTIM_DRY if dry else 0) | (0 if guard else _lib.OPTIM_NO_GUARD)
+    check(_lib.load().icka_optim_prepare(_ptr(partials), int(n), float(max_norm), flags, state.data_ptr(), _stream()),
+          "icka_optim_prepare")
+
+
+def optim_adamw_dev(flat, gflat, m, v, shadow, shadow16, table3: torch.Tensor, state: torch.Tensor) -> None:
+    """AdamW over the chunks of all groups with the values of the state block (skipped when its skip word is set)."""
+    for n, t in (("params", flat), ("grads", gflat), ("exp_avg", m), ("exp_avg_sq", v)):
+        _dev(t, n)
+        if t.dtype != F32 or t.numel() != flat.numel():
+            raise TypeError("optim_adamw_dev: %s must be f32 of the parameters' length" % n)
+    if table3.dtype != torch.int64 or table3.dim() != 2 or table3.shape[1] != 3 or not table3.is_contiguous():
+        raise TypeError("optim_adamw_dev: the chunk table is a contiguous int64 [n, 3] tensor (optim_chunk_table3)")
+    check(_lib.load().icka_optim_adamw_dev(flat.data_ptr(), gflat.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(shadow),
+                                           _ptr(shadow16), table3.data_ptr(), table3.shape[0], state.data_ptr(), _stream()),
+          "icka_optim_adamw_dev")
+
+
 # ------------------------------------------------------------------------------------------------- per-sample gates
 def sample_gate_fwd(a, c, gate, mode, out, B, S):
     _mat(a, "a"); _mat(out, "out")

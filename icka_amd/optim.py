@@ -18,6 +18,18 @@ Checkpoints: the moments and the step count live in flat arena-layout buffers, n
 ``state_dict()`` / ``load_state_dict()`` carry them (keys ``icka_m`` / ``icka_v`` / ``icka_t`` / ``icka_layout``), and a
 resumed run continues with the same bias correction.  A state saved for another arena layout is refused; a model whose arena
 is rebuilt after the first step (``.to()``, new Parameter objects) raises instead of silently restarting the moments.
+
+``ArenaAdamW(..., capturable=True)``: the update as graph nodes.  The host mode above passes the learning rate, the step count
+and both bias corrections as launch arguments, so a captured ``step()`` would freeze them.  The capturable mode keeps them in a
+device block (include/icka_hip.h: icka_optim_state): ``step()`` launches icka_optim_sqnorm, icka_optim_prepare (norm,
+non-finite test, clip coefficient, this update's rate and bias corrections, t += 1) and ONE icka_optim_adamw_dev for all
+groups, reads nothing from the device and passes no per-step host value -- ``train_step.TrainStep`` captures it behind the last
+micro-batch of an accumulation cycle.  The schedule (``schedule=None`` / ``"constant"`` / ``("linear", num_warmup_steps,
+num_training_steps)`` = get_linear_schedule_with_warmup) is evaluated on the device from t; ``param_groups[g]["lr"]`` is the
+BASE rate.  DO NOT attach a torch LR scheduler in this mode: it would rewrite the base rate on the host every step (uploaded
+only outside a capture), compounding with the device schedule in eager steps and doing nothing at all in replayed ones.
+With ``skip_nonfinite=True`` (default) a NaN / inf gradient norm refuses the update on the device: parameters, moments and
+shadows stay as they are, t does not advance, ``skipped_steps()`` counts it.
 """
 from __future__ import annotations
 
@@ -25,6 +37,7 @@ from typing import List, Optional
 
 import torch
 
+from . import _lib
 from . import kernels as K
 from .arena import _OPT_STEPS, ParamArena, arena_of
 
@@ -39,17 +52,63 @@ def reference_param_groups(model: torch.nn.Module, weight_decay: float = 0.01) -
             {"params": [p for n, p in named if any(nd in n for nd in NO_DECAY)], "weight_decay": 0.0}]
 
 
+def schedule_factor(kind: str, warmup: int, total: int, t: int) -> float:
+    """The factor the device applies to the base rate for update number t + 1 (csrc/optim.hip: optim_prepare_kernel), restated
+    in Python: "constant" -> 1; "linear" -> the lambda of transformers.get_linear_schedule_with_warmup(optimizer, warmup,
+    total) at scheduler step t (a LambdaLR starts at 0: with a warm-up the first update runs at rate 0)."""
+    if kind == "constant":
+        return 1.0
+    if kind != "linear":
+        raise ValueError("schedule kind %r: 'constant' or 'linear'" % (kind,))
+    if t < warmup:
+        return float(t) / float(max(1, warmup))
+    return max(0.0, float(total - t) / float(max(1, total - warmup)))
+
+
+def _parse_schedule(schedule):
+    if schedule is None or schedule == "constant":
+        return ("constant", 0, 0)
+    if isinstance(schedule, (tuple, list)) and len(schedule) == 3 and schedule[0] == "linear":
+        warmup, total = int(schedule[1]), int(schedule[2])
+        if warmup < 0 or total < 0:
+            raise ValueError("schedule ('linear', num_warmup_steps, num_training_steps): counts must be >= 0")
+        return ("linear", warmup, total)
+    raise ValueError("schedule: None, 'constant' or ('linear', num_warmup_steps, num_training_steps), got %r" % (schedule,))
+
+
 class ArenaAdamW(torch.optim.Optimizer):
     def __init__(self, model: torch.nn.Module, params=None, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.01, max_grad_norm: Optional[float] = None):
+                 weight_decay: float = 0.01, max_grad_norm: Optional[float] = None, capturable: bool = False, schedule=None,
+                 skip_nonfinite: bool = True):
         """``model``: the module whose forward built (or will build) the ParamArena.  ``params``: parameters or param groups
         (default: ``reference_param_groups(model, weight_decay)``).  ``max_grad_norm``: clip the global gradient norm inside
-        ``step()`` (the reference's clip_grad_norm_(..., 1.0)); None = no clipping."""
+        ``step()`` (the reference's clip_grad_norm_(..., 1.0)); None = no clipping.
+
+        ``capturable=True`` (module docstring): step count, schedule and bias corrections live on the device and ``step()`` can
+        be captured into a graph; at most 8 parameter groups.  ``schedule`` and ``skip_nonfinite`` belong to this mode
+        (``schedule`` is refused without it).  A torch LR scheduler must NOT be attached in this mode: ``lr`` is the base rate
+        of the device schedule.  Host edits of ``lr`` / ``betas`` / ``eps`` / ``weight_decay`` reach the device at the next
+        ``step()`` made outside a capture, or at once with ``sync_hyperparameters()``.  ``grad_norm()`` stays a device scalar;
+        ``current_lr()``, ``steps_taken()`` and ``skipped_steps()`` read the device block and are the only calls that
+        synchronise.  Before capturing ``step()`` by hand, call ``prepare_capture()`` once with the gradients in place."""
         if params is None:
             params = reference_param_groups(model, weight_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.model = model
         self.max_grad_norm = max_grad_norm
+        self.capturable = bool(capturable)
+        if not self.capturable and schedule is not None:
+            raise ValueError("ArenaAdamW(schedule=) belongs to capturable=True; in host mode a torch LR scheduler drives 'lr'")
+        if self.capturable and len(self.param_groups) > _lib.OPTIM_MAX_GROUPS:
+            raise ValueError("ArenaAdamW(capturable=True): at most %d parameter groups, got %d"
+                             % (_lib.OPTIM_MAX_GROUPS, len(self.param_groups)))
+        self.schedule = _parse_schedule(schedule)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._state = None       # capturable: the icka_optim_state block (uint8 device tensor); t lives there once bound
+        self._uploaded = None    # capturable: the hyperparameters the device block holds
+        self._table3 = None
+        self._table_cache = {}   # capturable: tables per gradient set, kept alive (a captured step() reads their addresses)
+        self._dry = False        # capturable: launches that apply nothing (train_step.TrainStep's warm-up)
         self._arena: Optional[ParamArena] = None
         self._m = self._v = None
         self._t = 0
@@ -66,6 +125,8 @@ class ArenaAdamW(torch.optim.Optimizer):
         if A.device.type != "cuda":
             raise RuntimeError("ArenaAdamW: the model's parameters are on %s (icka_amd has no CPU path)" % A.device)
         if A is not self._arena:
+            if self._arena is not None and self.capturable:
+                self._t = int(K.optim_state_read(self._state).t)
             if self._arena is not None and self._t > 0:
                 raise RuntimeError("ArenaAdamW: the model's parameter arena was rebuilt after %d optimizer steps (.to() / new "
                                    "Parameter objects): the moment buffers belong to the old layout.  Save state_dict() before "
@@ -75,6 +136,11 @@ class ArenaAdamW(torch.optim.Optimizer):
             self._v = torch.zeros(A.total, dtype=torch.float32, device=A.device)
             self._clip = torch.ones(2, dtype=torch.float32, device=A.device)
             self._sig = None
+            if self.capturable:
+                self._state = K.optim_state_new(A.device)
+                self._uploaded = None
+                self._table_cache = {}
+                self._write_t(self._t)
             if self._pending is not None:       # a state loaded before the arena existed
                 self._install(A, self._pending)
                 self._pending = None
@@ -92,7 +158,7 @@ class ArenaAdamW(torch.optim.Optimizer):
             sd["icka_layout"] = self._layout(self._arena)
         elif self._pending is not None:
             sd["icka_m"], sd["icka_v"], sd["icka_layout"] = self._pending["icka_m"], self._pending["icka_v"], self._pending["icka_layout"]
-        sd["icka_t"] = int(self._t)
+        sd["icka_t"] = self.steps_taken() if self._state is not None else int(self._t)
         return sd
 
     def load_state_dict(self, state_dict):
@@ -102,6 +168,8 @@ class ArenaAdamW(torch.optim.Optimizer):
                              "would silently restart)")
         super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("icka_")})
         self._t = int(extra["icka_t"])
+        if self._state is not None:
+            self._write_t(self._t)
         if "icka_m" in extra:
             if self._arena is not None:
                 self._install(self._arena, extra)
@@ -138,18 +206,105 @@ class ArenaAdamW(torch.optim.Optimizer):
             per_group.append(ranges)
             every += ranges
         sig = tuple(sig)
-        if sig != self._sig:
+        if sig != self._sig and self.capturable:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ArenaAdamW(capturable=True): the set of parameters that hold a gradient %s; inside a capture "
+                                   "step() cannot build its chunk tables (call prepare_capture() or one step() outside the "
+                                   "capture, with the same gradients in place)"
+                                   % ("changed" if self._sig is not None else "is not known yet"))
+            hit = self._table_cache.get(sig)
+            if hit is None:
+                norm = K.dp_chunk_table(sorted(every), A.device)
+                hit = self._table_cache[sig] = (norm, K.optim_chunk_table3([sorted(r) for r in per_group], A.device),
+                                                torch.empty(max(1, norm.shape[0]), dtype=torch.float32, device=A.device))
+            self._sig = sig
+            self._norm_table, self._table3, self._partials = hit
+        elif sig != self._sig:
             self._sig = sig
             self._tables = [K.dp_chunk_table(sorted(r), A.device) for r in per_group]
             self._norm_table = K.dp_chunk_table(sorted(every), A.device)
             self._partials = torch.empty(max(1, self._norm_table.shape[0]), dtype=torch.float32, device=A.device)
 
+    # ------------------------------------------------------------------------------------------------------------ capturable mode
+    def _need_capturable(self, what: str) -> None:
+        if not self.capturable:
+            raise RuntimeError("ArenaAdamW.%s belongs to capturable=True" % what)
+
+    def _write_t(self, t: int) -> None:
+        self._state[0:8].view(torch.int64).copy_(torch.tensor([int(t)], dtype=torch.int64))
+
+    def _hyperparameters(self):
+        return (self.schedule,) + tuple((float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                         float(g["weight_decay"])) for g in self.param_groups)
+
+    def sync_hyperparameters(self) -> None:
+        """Upload the schedule and every group's ``lr`` (the base rate) / ``betas`` / ``eps`` / ``weight_decay`` into the
+        device block now (``step()`` does so by itself when they changed, but only outside a capture)."""
+        self._need_capturable("sync_hyperparameters()")
+        self._bind()
+        if len(self.param_groups) > _lib.OPTIM_MAX_GROUPS:
+            raise ValueError("ArenaAdamW(capturable=True): at most %d parameter groups" % _lib.OPTIM_MAX_GROUPS)
+        h = _lib.OptimState()
+        kind, h.warmup, h.total = self.schedule
+        h.kind = _lib.OPTIM_SCHEDULE_LINEAR if kind == "linear" else _lib.OPTIM_SCHEDULE_CONSTANT
+        h.n_groups = len(self.param_groups)
+        hp = self._hyperparameters()
+        for i, (lr, b1, b2, eps, wd) in enumerate(hp[1:]):
+            h.base_lr[i], h.beta1[i], h.beta2[i], h.eps[i], h.weight_decay[i] = lr, b1, b2, eps, wd
+        K.optim_state_write(self._state, h, _lib.OptimState.HOST_LO, _lib.OptimState.HOST_HI)
+        self._uploaded = hp
+
+    def prepare_capture(self) -> None:
+        """Bind the arena, upload the hyperparameters and build the chunk tables for the gradients held NOW, launching
+        nothing: what a hand-made capture of ``step()`` needs beforehand (``train_step.TrainStep`` warms up by itself)."""
+        self._need_capturable("prepare_capture()")
+        A = self._bind()
+        self._build(A)
+        self.sync_hyperparameters()
+
+    def _read_state(self):
+        self._need_capturable("device-state reads")
+        self._bind()
+        return K.optim_state_read(self._state)
+
+    def steps_taken(self) -> int:
+        """Updates applied so far (t of the device block; synchronises).  Host mode: the host counter."""
+        if self._state is None:          # host mode, or not bound yet (a loaded count waits on the host)
+            return int(self._t)
+        return int(K.optim_state_read(self._state).t)
+
+    def skipped_steps(self) -> int:
+        """Updates the device refused because the gradient norm was not finite (synchronises)."""
+        return int(self._read_state().skipped)
+
+    def current_lr(self) -> List[float]:
+        """Per group, the rate the last applied update used, as the device computed it (synchronises; zeros before the
+        first update)."""
+        st = self._read_state()
+        return [float(st.lr[i]) for i in range(len(self.param_groups))]
+
+    def _step_capturable(self, A: ParamArena) -> None:
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing and self._uploaded != self._hyperparameters():
+            self.sync_hyperparameters()
+        n = self._norm_table.shape[0]
+        K.optim_sqnorm(A.gflat, self._norm_table, self._partials)
+        K.optim_prepare(self._partials, n, float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0, self._state,
+                        dry=self._dry, guard=self.skip_nonfinite)
+        K.optim_adamw_dev(A.flat, A.gflat, self._m, self._v, A.shadow, A.shadow16, self._table3, self._state)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self.capturable and self._uploaded is None and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ArenaAdamW(capturable=True): call prepare_capture() (or one step()) before capturing step()")
         A = self._bind()
         self._build(A)
         if self._norm_table.shape[0] == 0:
+            return loss
+        if self.capturable:
+            self._step_capturable(A)
+            self._mark_shadows_fresh(A)
             return loss
         lib = K._lib.load()
         st = K._stream()
@@ -170,15 +325,23 @@ class ArenaAdamW(torch.optim.Optimizer):
             K.check(lib.icka_optim_adamw(A.flat.data_ptr(), A.gflat.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), sh, sh16,
                                          table.data_ptr(), table.shape[0], coef, float(group["lr"]), float(b1), float(b2),
                                          float(group["eps"]), float(group["weight_decay"]), self._t, st), "icka_optim_adamw")
+        self._mark_shadows_fresh(A)
+        return loss
+
+    @staticmethod
+    def _mark_shadows_fresh(A: ParamArena) -> None:
         # every GEMM operand that changed got its 16-bit shadows from the update kernel itself (embedding tables have none):
         # tell the arena, so that the "tracked" policy does not re-cast after this step (the global post-step hook bumps
-        # _OPT_STEPS by one right after this method returns; parameters not in any group / without gradient did not change)
+        # _OPT_STEPS by one right after step() returns; parameters not in any group / without gradient did not change)
         v = _OPT_STEPS[0] + 1
         for s in A.order:
             v += s.param._version
         A._synced = v
-        return loss
 
     def grad_norm(self) -> torch.Tensor:
-        """Total gradient norm of the last clipped step (device scalar, as clip_grad_norm_ returns it)."""
+        """Total gradient norm of the last clipped step (device scalar, as clip_grad_norm_ returns it).  Capturable mode: of
+        the last step, clipped or not -- the norm word of the device block."""
+        if self.capturable:
+            self._bind()
+            return self._state[_lib.OptimState.norm.offset:_lib.OptimState.norm.offset + 4].view(torch.float32)[0]
         return self._clip[0]

@@ -45,7 +45,8 @@ extern "C" {
  *    `flags`; icka_attn_bwd, icka_lstm_fwd and icka_lstm_bwd take `flags`; the 256x256-tile and persistent 12-wave GEMM kernels
  *    those setters switched on left the library (profiles/NEGATIVE_RESULTS.md); icka_gemm_ln, icka_gemm_ln_sync_words, icka_gemm_ln_test_hooks, icka_gemm_qkv_attn (additive).
  *    Later, still 6: icka_contrastive_fwd, icka_contrastive_bwd, icka_contrastive_workspace_floats, icka_relu_bwd,
- *    icka_sample_swap (additive: the auxiliary objective of the gated taggers, csrc/objective.hip). */
+ *    icka_sample_swap (additive: the auxiliary objective of the gated taggers, csrc/objective.hip); icka_optim_prepare,
+ *    icka_optim_adamw_dev and the icka_optim_state block (additive: the capturable parameter update). */
 #define ICKA_ABI_VERSION 6
 int icka_abi_version(void);
 const char* icka_build_arch(void);
@@ -848,6 +849,54 @@ int icka_optim_clip(const float* partials, int32_t n, float max_norm, float* out
 int icka_optim_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, void* shadow_f16,
                      const int64_t* table_dev, int32_t n_chunks, const float* clip_coef, float lr, float beta1, float beta2,
                      float eps, float weight_decay, int32_t step, void* stream);
+
+/* The same update with the step count, the learning-rate schedule and the bias corrections held on the DEVICE, so that it can be
+ * captured into a graph with the step it follows (icka_amd/optim.py: ArenaAdamW(capturable=True); icka_amd/train_step.py).
+ * Added under ABI version 6.  The state block is one 8-byte-aligned device buffer of this layout; "device" fields are written
+ * by icka_optim_prepare only, "host" fields by the caller (uploaded outside a capture), never by a kernel:
+ *   t, skipped       device  updates applied / updates refused for a non-finite gradient norm (the host writes t on resume)
+ *   norm, coef       device  total gradient norm of the last prepare, and its clip coefficient
+ *   skip             device  1: the update launch behind this prepare returns without touching memory
+ *   kind..total      host    schedule: factor(t) = 1 (CONSTANT) or get_linear_schedule_with_warmup's lambda (LINEAR):
+ *                            t / max(1, warmup) for t < warmup, else max(0, (total - t) / max(1, total - warmup))
+ *   n_groups, base_lr, beta1, beta2, eps, weight_decay   host   per weight-decay group, at most ICKA_OPTIM_MAX_GROUPS
+ *   lr, bc1, bc2_sqrt   device  what update number t + 1 uses: (float)(base_lr * factor(t)) with factor in double (a LambdaLR
+ *                            hands the host-mode kernel the same float), 1 - beta1^(t+1), sqrt(1 - beta2^(t+1)) */
+#define ICKA_OPTIM_MAX_GROUPS 8
+#define ICKA_OPTIM_SCHEDULE_CONSTANT 0
+#define ICKA_OPTIM_SCHEDULE_LINEAR 1
+#define ICKA_OPTIM_DRY 1        /* prepare flag: set skip, change nothing else (warm-up launches ahead of a capture) */
+#define ICKA_OPTIM_NO_GUARD 2   /* prepare flag: apply the update also when the norm is not finite */
+typedef struct icka_optim_state {
+    int64_t t;
+    int64_t skipped;
+    float norm;
+    float coef;
+    int32_t skip;
+    int32_t reserved;
+    int32_t kind;
+    int32_t n_groups;
+    int64_t warmup;
+    int64_t total;
+    double base_lr[ICKA_OPTIM_MAX_GROUPS];
+    float beta1[ICKA_OPTIM_MAX_GROUPS];
+    float beta2[ICKA_OPTIM_MAX_GROUPS];
+    float eps[ICKA_OPTIM_MAX_GROUPS];
+    float weight_decay[ICKA_OPTIM_MAX_GROUPS];
+    float lr[ICKA_OPTIM_MAX_GROUPS];
+    float bc1[ICKA_OPTIM_MAX_GROUPS];
+    float bc2_sqrt[ICKA_OPTIM_MAX_GROUPS];
+} icka_optim_state;
+/*   icka_optim_prepare:   one block, after icka_optim_sqnorm (n = 0: no partials, norm 0).  Sums the partials in
+ *                         icka_optim_clip's order (bitwise the same norm).  A finite sum: writes norm, coef (max_norm <= 0: 1),
+ *                         lr / bc1 / bc2_sqrt of every group for update t + 1, advances t, clears skip.  A non-finite sum:
+ *                         sets skip, skipped += 1; t and the per-step values stay.  t therefore advances exactly once per
+ *                         applied update, in this launch; no launch behind the update is needed.
+ *   icka_optim_adamw_dev: icka_optim_adamw's arithmetic and shadow stores for the chunks of ALL groups in one launch: the table
+ *                         has three int64 per chunk {first element, count, group}; every block reads skip first. */
+int icka_optim_prepare(const float* partials, int32_t n, float max_norm, int32_t flags, void* state, void* stream);
+int icka_optim_adamw_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, void* shadow_f16,
+                         const int64_t* table3_dev, int32_t n_chunks, const void* state, void* stream);
 
 #ifdef __cplusplus
 }
