@@ -18,6 +18,7 @@ c_vp, c_i32, c_i64, c_u64, c_f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64,
 ABI_VERSION = 6   # include/icka_hip.h: ICKA_ABI_VERSION (load() refuses a library built from another header)
 GEMM_NT, GEMM_NN, GEMM_TN, GEMM_TT = 0, 1, 2, 3
 ATTN_FP8, ATTN_TILED = 1, 2                               # flags of icka_attn_fwd_ex / icka_attn_bwd
+ATTN_PROBS_HEAD_MEAN = 1                                  # flag of icka_attn_probs
 LSTM_PER_STEP, LSTM_TICKETS, LSTM_NO_BATCH_SPLIT = 1, 2, 4   # flags of icka_lstm_fwd / icka_lstm_bwd
 EPI_NONE, EPI_GELU, EPI_DGELU, EPI_ADD, EPI_GATE, EPI_TANH, EPI_RELU, EPI_ADD_RELU = 0, 1, 2, 3, 4, 5, 6, 7
 
@@ -159,6 +160,7 @@ PROTOTYPES = {
     "icka_attn_bwd":(c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,
                               c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_u64,
                               c_vp, c_i32, c_vp]),
+    "icka_attn_probs": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp]),
     "icka_cast_f32_to_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "icka_cast_to_f16": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp]),
     "icka_cast_f32_to_bf16_f16": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp]),

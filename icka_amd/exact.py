@@ -25,6 +25,7 @@ import torch
 from . import _lib
 from ._lib import GEMM_NN, GEMM_NT, GEMM_TN, GEMM_TT, XGemmDesc, check
 from .arena import ParamArena
+from .attention_maps import current as _maps_recorder
 
 F32 = torch.float32
 ACT_GELU, ACT_TANH, ACT_GATE = 0, 1, 2
@@ -213,6 +214,9 @@ def _linear_bwd_params(A: ParamArena, dy, x, ws, bs) -> None:
 
 def _attn_core_fwd(A: ParamArena, sa, x, kv_src, add_mask, d, Skv: int, save: bool):
     """BertSelfAttention / BertCoAttention (:478-506, :590-624).  Returns (ctx [M,H], saved)."""
+    rec = _maps_recorder()
+    if rec is not None:      # attention maps are recorded in the 16-bit modes only
+        rec.refuse_fp32(sa)
     M, H = x.shape
     B, h, S = d.B, d.heads, d.S
     dh = H // h

@@ -65,6 +65,7 @@ import torch
 from . import crf
 from . import kernels as K
 from . import packing
+from .attention_maps import active as _maps_active
 
 
 def _sig(values) -> tuple:
@@ -581,12 +582,16 @@ class GraphedStep(object):
             values = None
             sigkey = self._last.inputs.signature() if self._last.inputs is not None else None
         key = (sigkey, training)
-        cap = self._caps.get(key)
+        # attention maps are recorded from eager launches (the graphs hold no probability launch): under a recorder the call
+        # takes the eager route below as it is -- no capture, no replay
+        recording = _maps_active()
+        cap = None if recording else self._caps.get(key)
         if cap is None:
             src = values
             if src is None and self._last.inputs is not None:
                 src = list(self._last.inputs.static)           # gs() in the other mode: on the buffers as they are
-            cap = self._new_capture(key, src)
+            if not recording:
+                cap = self._new_capture(key, src)
             if cap is None:
                 self.stats["eager_calls"] += 1
                 if src is None:
@@ -955,6 +960,8 @@ class GraphedModule(object):
     def __call__(self, *args, **kwargs):
         if self._caps is None:
             raise RuntimeError("GraphedModule is closed")
+        if _maps_active():      # attention maps are recorded from eager launches: no capture, no replay
+            return self._eager(args, kwargs)
         kwkeys = tuple(sorted(kwargs))
         kwvalues = [kwargs[k] for k in kwkeys]
         values = list(args) + kwvalues

@@ -703,6 +703,42 @@ def attn_bwd(q, k, v, add_mask, out, dout, lse, delta, dq, dk, dv, B, heads, Sq,
                             _ptr(keepbits), _lib.ATTN_TILED if tiled else 0, _stream()), "icka_attn_bwd")
 
 
+ATTN_PROBS_MAX_KEYS = 512   # icka_attn_probs keeps every score of a query row in registers: BERT's position limit
+
+
+def attn_probs(q, k, add_mask, B, heads, Sq, Skv, *, head_mean=False, scale=None, out=None) -> torch.Tensor:
+    """Attention maps (icka_attn_probs): softmax(scale * q.k^T + add_mask) BEFORE dropout, f32 [B,heads,Sq,Skv] or, with
+    ``head_mean``, the mean over heads [B,Sq,Skv].  q / k: the 2-D row-major bf16 views attn_fwd takes ([>= B*Sq, >= heads*64]
+    and [>= B*Skv, >= heads*64], head size 64), add_mask: contiguous f32 [B,Skv].  ``out``: a contiguous f32 device tensor
+    of exactly that many elements to write into (else a new one).  One launch; 1 <= Skv <= 512."""
+    for n, t in (("q", q), ("k", k)):
+        _mat(t, n)
+    for n, v in (("B", B), ("heads", heads), ("Sq", Sq), ("Skv", Skv)):
+        if int(v) != v or v < 1:
+            raise ValueError("%s must be a positive integer, got %r" % (n, v))
+    if Skv > ATTN_PROBS_MAX_KEYS:
+        raise ValueError("attn_probs holds a query's scores in registers: Skv <= %d, got %d" % (ATTN_PROBS_MAX_KEYS, Skv))
+    for n, t, rows in (("q", q, B * Sq), ("k", k, B * Skv)):
+        if t.shape[0] < rows or t.shape[1] < heads * 64:
+            raise ValueError("%s must hold at least %d rows and heads * 64 = %d columns, got %s" % (n, rows, heads * 64, tuple(t.shape)))
+    _dev(add_mask, "add_mask")
+    if add_mask.dtype != F32 or not add_mask.is_contiguous() or add_mask.numel() != B * Skv:
+        raise ValueError("add_mask must be contiguous f32 [B, Skv] = [%d, %d]" % (B, Skv))
+    shape = (B, Sq, Skv) if head_mean else (B, heads, Sq, Skv)
+    if out is None:
+        out = torch.empty(shape, dtype=F32, device=q.device)
+    else:
+        _dev(out, "out")
+        if out.dtype != F32 or not out.is_contiguous() or out.numel() != math.prod(shape):
+            raise ValueError("out must be a contiguous f32 tensor of %d elements" % math.prod(shape))
+    if not (q.device == k.device == add_mask.device == out.device):
+        raise ValueError("attn_probs: q, k, add_mask and out must live on one device")
+    check(_lib.load().icka_attn_probs(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), add_mask.data_ptr(), out.data_ptr(),
+                                      B, heads, Sq, Skv, (1.0 / 8.0) if scale is None else scale,
+                                      _lib.ATTN_PROBS_HEAD_MEAN if head_mean else 0, _stream()), "icka_attn_probs")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- packed batches
 def _i32vec(t: torch.Tensor, n: int, name: str) -> None:
     _dev(t, name)

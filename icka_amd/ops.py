@@ -17,6 +17,7 @@ import torch
 
 from . import kernels as K
 from .arena import ParamArena
+from .attention_maps import current as _maps_recorder
 
 BF16, F32, F16 = torch.bfloat16, torch.float32, torch.float16
 import os as _os
@@ -238,6 +239,12 @@ def _attn_core_fwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
     M, H = x.shape
     h16 = x16 is not None
     xa = x16 if h16 else x
+    # attention maps (attention_maps.py): with a recorder active on this thread and ``sa`` selected, every return below follows its
+    # attention launch with one probability launch on the same q / k / mask; nothing else of the call changes
+    rec = _maps_recorder()
+    rec_name = None if rec is None else rec.wants(sa, H // d.heads, Skv)
+    if rec_name is not None and d.pack is not None:
+        raise NotImplementedError("attention_maps does not record packed batches (set_packed)")
     if kv_src is None:
         qkv = _empty(x, M, 3 * H)
         wq = (sa.query.weight, sa.key.weight, sa.value.weight)
@@ -255,6 +262,8 @@ def _attn_core_fwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
             kb = K.attn_keepbits(d.B, d.heads, d.S, Skv, x.device) if want_kb else None
             if K.gemm_qkv_attn(xa, A.w16_cat(wq) if h16 else A.w_cat(wq), bq, qkv, add_mask, ctx, lse, d.B, d.heads, d.S,
                                p_drop=d.p_attn, seed=seed_a, out16=ctx16, keepbits=kb):
+                if rec_name is not None:
+                    rec.record(rec_name, qkv[:, :H], qkv[:, H:2 * H], add_mask, d.B, d.heads, d.S, Skv)
                 return ctx, ctx16, ((qkv, None, lse, seed_a, kb) if save else None)
             pre = (ctx, seed_a, lse, ctx16, kb)      # not a shape of the fused launch: the two launches below, same seed and buffers
         K.gemm(K.GEMM_NT, xa, A.w16_cat(wq) if h16 else A.w_cat(wq), qkv, bias=bq)
@@ -294,6 +303,8 @@ def _attn_core_fwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
         return ctx, ctx16, ((qkv, kvbuf, lse, seed_a, kb) if save else None)
     K.attn_fwd(q, k, v, add_mask, ctx, lse, d.B, d.heads, d.S, Skv, p_drop=d.p_attn, seed=seed_a, fp8=fp8, out16=ctx16,
                keepbits=kb)
+    if rec_name is not None:
+        rec.record(rec_name, q, k, add_mask, d.B, d.heads, d.S, Skv)
     return ctx, ctx16, ((qkv, kvbuf, lse, seed_a, kb) if save else None)
 
 

@@ -40,6 +40,7 @@ from typing import Callable
 import torch
 
 from . import kernels as K
+from .attention_maps import active as _maps_active
 from .graph import _GradSnapshot, _StepBase, _end_capture_quietly, _sig
 from .optim import ArenaAdamW
 
@@ -154,7 +155,7 @@ class TrainStep(_StepBase):
             raise RuntimeError("TrainStep is closed")
         values = self._values(args, kwargs)
         last = self._pos == self.k - 1
-        if self._replayable(values):
+        if self._replayable(values) and not _maps_active():   # (attention maps are recorded from eager launches)
             self._prepare(False, values)
             key = _LAST if last else (_FIRST if self._pos == 0 else _MID)
             self._graphs[key].replay()

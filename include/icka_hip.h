@@ -349,6 +349,20 @@ int icka_attn_bwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const 
                   float* delta, void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, int32_t B,
                   int32_t heads, int32_t Sq, int32_t Skv, float scale, float p_drop, uint64_t seed, const void* keep_bits,
                   int32_t flags, void* stream);
+/* Attention maps (csrc/attn_probs.hip; additive, ABI version stays 6): the probabilities the fused kernels never materialise.
+ * P = softmax(scale * Q.K^T + add_mask[b, key]) -- the probabilities BEFORE dropout (:492-497, :606-611).
+ * Q / K: bf16 token-major as icka_attn_fwd (head size 64, element (b,s,head,e) at ptr[(b*S+s)*ld + head*64 + e]);
+ * add_mask f32 [B,Skv].  P f32, contiguous: [B,heads,Sq,Skv], or with ICKA_ATTN_PROBS_HEAD_MEAN [B,Sq,Skv] = the mean
+ * over heads, summed in head order 0..heads-1 inside the kernel (no atomics: the same bits on every run).
+ * The sample's largest mask value is subtracted from its mask row before the add (softmax is invariant under the shift; f32 is
+ * not: score - 10000 sits on a 2^-10 grid), so an all-masked sample gets the softmax of its unmasked scores at full precision.
+ * Mask values are meant to be finite (the reference's 0 / -10000); a sample whose mask row is -inf for every key gets NaN, as
+ * the reference's softmax gives.
+ * One launch.  Any Sq >= 1, 1 <= Skv <= 512 (BERT's position limit; more is ICKA_E_SHAPE); unknown flags ICKA_E_ARG;
+ * Q / K 16-byte aligned with ld % 8 == 0 and P 4-byte aligned, else ICKA_E_ALIGN.  Nothing is written past P's last element. */
+int icka_attn_probs(const void* Q, int64_t ldq, const void* K, int64_t ldk, const float* add_mask, float* P,
+                    int32_t B, int32_t heads, int32_t Sq, int32_t Skv, float scale, int32_t flags, void* stream);
+#define ICKA_ATTN_PROBS_HEAD_MEAN 1
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Packed (padding-free) batches, csrc/packed.hip + the varlen instances of the whole-head attention kernels.  The valid
