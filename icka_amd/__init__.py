@@ -23,6 +23,7 @@ from . import packing
 from .packing import PackOverflowError, TokenBudgetBatchSampler, set_packed
 from . import metrics
 from .metrics import ChunkEvaluator
+from .entities import EntityDecoder
 from .attention_maps import attention_maps   # (the name now denotes the recorder; the module stays importable by its path)
 
 __all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "BertConfig", "BertModel", "BertEmbeddings", "BertEncoder", "BertLayer", "BertLayerNorm", "BertPooler",
@@ -31,4 +32,4 @@ __all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "Bert
            "BertPreTrainedModel", "MTCCMBertForMMTokenClassificationCRF", "cls_layer_both", "scalar_gate_fusion",
            "token_ce_loss", "set_precision", "resolved_precision", "ParamArena", "cross_modal", "PromptRobertaModel",
            "GradReducer", "graph", "DevicePrefetcher", "GraphedModule", "GraphedStep", "TrainStep", "packing", "set_packed",
-           "PackOverflowError", "TokenBudgetBatchSampler", "metrics", "ChunkEvaluator", "attention_maps"]
+           "PackOverflowError", "TokenBudgetBatchSampler", "metrics", "ChunkEvaluator", "EntityDecoder", "attention_maps"]

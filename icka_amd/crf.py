@@ -237,3 +237,136 @@ class CRF(ArenaModule):
                      best)
         rows = best.cpu().tolist()
         return [[v for v in r if v >= 0] for r in rows]
+
+    # ------------------------------------------------------------------------------------------------- posteriors
+    def marginals(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``P(y_t = j | emissions)``, f32 in the layout of ``emissions`` ([B,S,C], or [S,B,C] without ``batch_first``): the
+        chain runs over position 0 and the positions with ``mask != 0``; the other positions hold exact zeros.  Detached;
+        one launch, no host sync."""
+        e, _, m = self._prep(emissions.detach(), None, mask)
+        self._arena()
+        B, S, Cn = e.shape
+        out = torch.empty(B, S, Cn, dtype=F32, device=e.device)
+        small = torch.empty(B + 1, dtype=torch.int32, device=e.device)     # log Z and the (unused: no path) refusal count
+        K.crf_posterior(e, m, self.start_transitions.detach(), self.end_transitions.detach(), self.transitions.detach(),
+                        small[:B].view(F32), small[B:], marginals=out)
+        return out if self.batch_first else out.transpose(0, 1)
+
+    def _paths_into(self, tags: DeviceTags, paths, m: Optional[torch.Tensor], B: int, S: int) -> None:
+        """Write ``paths`` (DeviceTags | integer [B,S] device tensor | per-sample lists) into ``tags`` without a host sync."""
+        if isinstance(paths, DeviceTags):
+            if paths.batch_size != B:
+                raise ValueError("paths hold %d samples for a batch of %d" % (paths.batch_size, B))
+            n = min(paths.capacity, tags.capacity)
+            tags.lens.copy_(paths.lens)
+            tags.tags_flat[:n].copy_(paths.tags_flat[:n])
+            tags.deferred_check = paths.deferred_check
+        elif isinstance(paths, torch.Tensor):
+            if not self.batch_first:
+                paths = paths.transpose(0, 1)
+            if paths.is_floating_point() or tuple(paths.shape) != (B, S) or paths.device != tags.lens.device:
+                raise ValueError("paths must be an integer [B, S] tensor on the device of the emissions, got %s %s on %s"
+                                 % (paths.dtype, tuple(paths.shape), paths.device))
+            dev, cap = paths.device, tags.capacity
+            if m is None:
+                lens = torch.full((B,), S, dtype=torch.int64, device=dev)
+            else:
+                lens = m[:, 1:].sum(1) + 1                                  # position 0 is always on
+            ar = torch.arange(S, device=dev)
+            idx = (lens.cumsum(0) - lens)[:, None] + ar[None, :]
+            idx = torch.where(ar[None, :] < lens[:, None], idx, torch.full_like(idx, cap))   # the rest of a row: a spare slot
+            tmp = torch.empty(cap + 1, dtype=torch.int32, device=dev)
+            tmp.scatter_(0, idx.reshape(-1), paths.reshape(-1).to(torch.int32))
+            tags.lens.copy_(lens)
+            tags.tags_flat.copy_(tmp[:cap])
+        else:
+            rows = [list(r) for r in paths]
+            if len(rows) != B or sum(len(r) for r in rows) > tags.capacity:
+                raise ValueError("paths hold %d samples / %d tags for a batch of %d x %d"
+                                 % (len(rows), sum(len(r) for r in rows), B, S))
+            flat = [int(v) for r in rows for v in r]
+            tags.lens.copy_(torch.tensor([len(r) for r in rows], dtype=torch.int32))
+            if flat:
+                tags.tags_flat[:len(flat)].copy_(torch.tensor(flat, dtype=torch.int32))
+
+    def posterior(self, emissions: torch.Tensor, paths=None, mask: Optional[torch.Tensor] = None, *,
+                  marginals: bool = False, label_table=None) -> "CrfPosterior":
+        """How sure the model is of ``paths`` (default: of its own Viterbi paths): ``log_z``, ``seq_logp``, ``token_conf``
+        and, with ``marginals=True``, the token marginals; with ``label_table`` (the words of ``metrics.label_table``) the
+        chunks of every path and their exact posteriors.  The definitions are written out in include/icka_hip.h.  A path has
+        one tag per on-position (position 0 and the positions with ``mask != 0``): what ``decode`` returns for the same mask.
+        ``paths``: a ``DeviceTags``, an integer device tensor in the layout of the mask (the first L entries of each sample),
+        per-sample lists, or None: then ``icka_crf_score_decode`` runs first (two launches in all).  Outside autograd, no host
+        sync; a sample whose path does not fit its mask or holds a tag id outside [0, num_tags) is refused (NaN outputs,
+        counted in ``bad``)."""
+        e, _, m = self._prep(emissions.detach(), None, mask)
+        self._arena()
+        B, S, Cn = e.shape
+        if S * Cn > K.CRF_MAX_SC or B > K.CRF_FLAT_MAX_B:
+            raise ValueError("CRF.posterior: B <= %d and S * num_tags <= %d, got [%d, %d, %d]"
+                             % (K.CRF_FLAT_MAX_B, K.CRF_MAX_SC, B, S, Cn))
+        if m is not None:
+            m[:, 0] = 1            # (m is _prep's own copy) position 0 is on: decode and posterior count the same path length
+        if label_table is not None and not isinstance(label_table, torch.Tensor):
+            label_table = torch.tensor(list(label_table), dtype=torch.int32).to(e.device)
+        post = CrfPosterior(B, S, e.device, label_table is not None)
+        post.bad.zero_()
+        P = (self.start_transitions.detach(), self.end_transitions.detach(), self.transitions.detach())
+        if paths is None:
+            K.crf_score_decode(e, None, m, *P, None, post.tags.lens, post.tags.tags_flat)
+        else:
+            self._paths_into(post.tags, paths, m, B, S)
+        mg = torch.empty(B, S, Cn, dtype=F32, device=e.device) if marginals else None
+        K.crf_posterior(e, m, *P, post.log_z, post.bad, lens=post.tags.lens, tags_flat=post.tags.tags_flat,
+                        seq_logp=post.seq_logp, token_conf=post.token_conf, marginals=mg, label_table=label_table,
+                        ent=post.ent, ent_conf=post.ent_conf, n_ent=post.n_ent)
+        if mg is not None:
+            post.marginals = mg if self.batch_first else mg.transpose(0, 1)
+        return post
+
+
+class CrfPosterior(object):
+    """The outputs of ``CRF.posterior`` on the device, all but the marginals in ONE buffer (``joint``, int32 words; the f32
+    fields are views of it) so that ``host()`` is one device-to-host copy:
+
+        bad int32 [1] | tags.lens int32 [B] | tags.tags_flat int32 [B*S] | n_ent int32 [B] | ent int32 [B*S, 3] |
+        log_z f32 [B] | seq_logp f32 [B] | token_conf f32 [B*S] | ent_conf f32 [B*S]
+
+    ``tags`` is a ``DeviceTags``; ``token_conf`` is aligned with ``tags.tags_flat``; chunk k of sample b sits at row
+    ``sum(lens[:b]) + k`` of ``ent`` (type id, start, end exclusive; path coordinates) and ``ent_conf``, ``n_ent[b]`` rows per
+    sample (only with a label table: else these three are None).  ``marginals``: None unless asked for."""
+
+    def __init__(self, B: int, S: int, device, entities: bool):
+        cap = B * S
+        sizes = [("bad", 1), ("lens", B), ("tags_flat", cap), ("n_ent", B if entities else 0), ("ent", 3 * cap if entities else 0),
+                 ("log_z", B), ("seq_logp", B), ("token_conf", cap), ("ent_conf", cap if entities else 0)]
+        self.slices, o = {}, 0
+        for name, n in sizes:
+            self.slices[name] = (o, o + n)
+            o += n
+        self.joint = torch.empty(o, dtype=torch.int32, device=device)
+        part = lambda name: self.joint[self.slices[name][0]:self.slices[name][1]]
+        self.batch_size, self.capacity = B, cap
+        self.bad = part("bad")
+        self.tags = DeviceTags(part("lens"), part("tags_flat"))
+        self.log_z, self.seq_logp, self.token_conf = (part(n).view(F32) for n in ("log_z", "seq_logp", "token_conf"))
+        self.n_ent = part("n_ent") if entities else None
+        self.ent = part("ent").view(cap, 3) if entities else None
+        self.ent_conf = part("ent_conf").view(F32) if entities else None
+        self.marginals = None
+
+    def host(self) -> dict:
+        """Everything but the marginals on the host, as python lists keyed by field name: the one device-to-host copy (a host
+        sync).  Runs the check the producer of the paths deferred, if any."""
+        h = self.joint.cpu()
+        if self.tags.deferred_check is not None:
+            self.tags.deferred_check()
+        out = {}
+        for name, (a, b) in self.slices.items():
+            out[name] = (h[a:b].view(F32) if name in ("log_z", "seq_logp", "token_conf", "ent_conf") else h[a:b]).tolist()
+        out["bad"] = out["bad"][0]
+        return out
+
+    def __repr__(self) -> str:
+        return "CrfPosterior(batch=%d, capacity=%d, entities=%s, device=%s)" % (
+            self.batch_size, self.capacity, self.ent is not None, self.joint.device)

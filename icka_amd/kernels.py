@@ -1034,6 +1034,74 @@ def check_flat_tags(lens, tags_flat, B, S):
         raise ValueError("tags_flat holds %d tags, a batch of %d x %d needs up to %d" % (tags_flat.numel(), B, S, B * S))
 
 
+CRF_MAX_SC, CRF_POSTERIOR_MAX_S, CRF_POSTERIOR_MAX_IDS = 12288, 512, 64
+
+
+def crf_posterior(emissions, mask, start, end, trans, log_z, bad, *, lens=None, tags_flat=None, seq_logp=None,
+                  token_conf=None, marginals=None, label_table=None, ent=None, ent_conf=None, n_ent=None):
+    """log Z, token marginals and -- for the paths ``lens`` + ``tags_flat`` (a ``crf.DeviceTags``) -- the path's
+    log-probability, the marginal of every path tag and, with a ``label_table``, the path's chunks with their posteriors
+    (icka_crf_posterior, include/icka_hip.h): one launch, no host sync.  ``bad`` (int32 [1]) is ADDED to: zero it first.
+    Every operand is checked on the host (dtype, shape, contiguity, the kernel's limits: ValueError; then the device:
+    TypeError) before anything is launched."""
+    def vec(t, name, dtype, shape=None, least=None):
+        ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
+        if ok and shape is not None:
+            ok = tuple(t.shape) == shape
+        if ok and least is not None:      # at least least[0] rows of the trailing shape least[1:]
+            ok = t.dim() == len(least) and t.shape[0] >= least[0] and tuple(t.shape[1:]) == tuple(least[1:])
+        if not ok:
+            want = shape if shape is not None else (">= %d" % least[0],) + tuple(least[1:])
+            raise ValueError("crf_posterior: %s must be a contiguous %s tensor of shape %s, got %s %s"
+                             % (name, dtype, want, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
+        return t
+
+    for n, t in (("emissions", emissions), ("start", start), ("end", end), ("trans", trans)):
+        if not isinstance(t, torch.Tensor) or t.dtype != F32 or not t.is_contiguous():
+            raise ValueError("crf_posterior: %s must be contiguous f32" % n)
+    if emissions.dim() != 3:
+        raise ValueError("crf_posterior: emissions must be [B,S,C], got %s" % (tuple(emissions.shape),))
+    B, S, Cn = emissions.shape
+    if start.numel() != Cn or end.numel() != Cn or tuple(trans.shape) != (Cn, Cn):
+        raise ValueError("crf_posterior: transition parameters do not match num_tags = %d" % Cn)
+    if B < 1 or S < 1 or not 1 <= Cn <= 64 or S * Cn > CRF_MAX_SC or B > CRF_FLAT_MAX_B:
+        raise ValueError("crf_posterior: B <= %d, C <= 64 and S * C <= %d, got [%d, %d, %d]"
+                         % (CRF_FLAT_MAX_B, CRF_MAX_SC, B, S, Cn))
+    used = [emissions, start, end, trans, vec(log_z, "log_z", F32, (B,)), vec(bad, "bad", torch.int32, (1,))]
+    if mask is not None:
+        used.append(vec(mask, "mask", torch.int64, (B, S)))
+    if marginals is not None:
+        used.append(vec(marginals, "marginals", F32, (B, S, Cn)))
+    if (lens is None) != (tags_flat is None):
+        raise ValueError("crf_posterior: lens and tags_flat go together")
+    cap, L_ids = 0, 0
+    if lens is not None:
+        used += [vec(lens, "lens", torch.int32, (B,)), vec(tags_flat, "tags_flat", torch.int32, least=(0,))]
+        cap = tags_flat.numel()
+        used += [vec(seq_logp, "seq_logp", F32, (B,)), vec(token_conf, "token_conf", F32, least=(cap,))]
+    elif seq_logp is not None or token_conf is not None or label_table is not None:
+        raise ValueError("crf_posterior: seq_logp, token_conf and label_table need the paths (lens + tags_flat)")
+    if label_table is not None:
+        vec(label_table, "label_table", torch.int32, least=(1,))
+        L_ids = label_table.numel()
+        if L_ids > CRF_POSTERIOR_MAX_IDS or S > CRF_POSTERIOR_MAX_S:
+            raise ValueError("crf_posterior: with a label table at most %d words and S <= %d, got %d words, S = %d"
+                             % (CRF_POSTERIOR_MAX_IDS, CRF_POSTERIOR_MAX_S, L_ids, S))
+        used += [label_table, vec(ent, "ent", torch.int32, least=(cap, 3)), vec(ent_conf, "ent_conf", F32, least=(cap,)),
+                 vec(n_ent, "n_ent", torch.int32, (B,))]
+    elif ent is not None or ent_conf is not None or n_ent is not None:
+        raise ValueError("crf_posterior: ent, ent_conf and n_ent need a label_table")
+    for t in used:
+        _dev(t, "crf_posterior operand")
+        if t.device != emissions.device:
+            raise ValueError("crf_posterior: operands on %s and %s" % (emissions.device, t.device))
+    check(_lib.load().icka_crf_posterior(emissions.data_ptr(), Cn, _ptr(mask), start.data_ptr(), end.data_ptr(),
+                                         trans.data_ptr(), _ptr(lens), _ptr(tags_flat), cap, _ptr(label_table), L_ids,
+                                         log_z.data_ptr(), _ptr(seq_logp), _ptr(token_conf), _ptr(marginals), _ptr(ent),
+                                         _ptr(ent_conf), _ptr(n_ent), bad.data_ptr(), B, S, Cn, _stream()),
+          "icka_crf_posterior")
+
+
 # ------------------------------------------------------------------------------------------------- chunk metrics
 CHUNK_EVAL_MAX_S, CHUNK_EVAL_MAX_IDS, CHUNK_EVAL_MAX_TYPES, CHUNK_EVAL_HEAD = 512, 64, 32, 6
 

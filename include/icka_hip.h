@@ -561,6 +561,38 @@ int icka_crf_decode(const float* emissions, int64_t ld, const int64_t* mask, con
 int icka_crf_score_decode(const float* emissions, int64_t ld, const int64_t* tags, const int64_t* mask,
                           const float* start, const float* end, const float* trans, float* llh, int32_t* lens,
                           int32_t* tags_flat, int64_t capacity, int32_t B, int32_t S, int32_t C, void* stream);
+/* CRF posteriors (csrc/crf_posterior.hip): how sure the model is of a tag path.  One launch, one wave per sample, no host
+ * sync.  Per sample the ON-POSITIONS are position 0 and every t >= 1 with mask[b,t] != 0 (mask NULL = all on), L their
+ * number, x_0 .. x_{L-1} the emission rows at them.  The model is the chain over the on-positions,
+ *   score(y) = start[y_0] + x_0[y_0] + sum_{i >= 1} (trans[y_{i-1}, y_i] + x_i[y_i]) + end[y_{L-1}],  Z = sum_y exp score(y).
+ * A PATH is L tag ids; the paths come as icka_crf_score_decode writes them: lens int32 [B], tags_flat int32 [capacity], path
+ * b at off_b = sum(lens[0 .. b-1]) (summed inside the kernel).  lens and tags_flat may both be NULL: then only log_z and
+ * marginals are written (seq_logp, token_conf and the chunk arguments are ignored).  Outputs, f32 unless noted:
+ *   log_z [B]          log Z
+ *   seq_logp [B]       score(path) - log Z  (<= 0)
+ *   token_conf         [capacity], aligned with tags_flat: P(y_i = path_i | x) at off_b + i
+ *   marginals          [B,S,C] contiguous, nullable: P(y_t = j | x) at on-positions, exact 0 at off-positions; every element
+ *                      of the sample is written
+ *   ent int32 [capacity,3], ent_conf [capacity], n_ent int32 [B]   only with label_table (else ignored): the chunks of the
+ *                      path by the rules of icka_chunk_eval below on the label_table words of its tags (nothing is skipped:
+ *                      bit 2 is not read; an id >= L_ids counts as the default tag), in PATH coordinates: chunk k of sample b
+ *                      at row off_b + k = (type id, start, end) with end exclusive, n_ent[b] chunks (at most lens[b], so every
+ *                      sample stays inside its own segment).  ent_conf = the exact posterior that the tags at path positions
+ *                      start .. end-1 equal the path's: alpha_s[y_s] prod_{i=s+1}^{e-1} psi_i(y_{i-1}, y_i) beta_{e-1}[y_{e-1}] / Z
+ *                      (psi_i(u, v) = exp(trans[u,v] + x_i[v])); a chunk of one token has its token_conf, bit for bit.
+ *                      Rows k >= n_ent[b] of a segment and everything past sum(lens) are not written.
+ *   bad int32 [1]      += the number of REFUSED samples (the caller zeroes it): lens[b] != L, a segment outside
+ *                      [0, capacity), or a tag id outside [0, C).  A refused sample gets NaN in log_z, seq_logp, its
+ *                      token_conf segment and its marginals, and n_ent[b] = 0; no load or store is indexed by an unchecked
+ *                      id; the other samples are unaffected.
+ * Limits (else ICKA_E_SHAPE, nothing launched): C <= 64, S*C <= 12288, B <= 2048; with label_table S <= 512 and
+ * 1 <= L_ids <= 64.  C <= 16 with S <= 512 runs the scaled linear-domain recursions in registers (samples whose
+ * normalisers leave the f32 range, or with L*C > 4096, are redone in the log domain), otherwise the log-domain form. */
+int icka_crf_posterior(const float* emissions, int64_t ld, const int64_t* mask, const float* start, const float* end,
+                       const float* trans, const int32_t* lens, const int32_t* tags_flat, int64_t capacity,
+                       const int32_t* label_table, int32_t L_ids, float* log_z, float* seq_logp, float* token_conf,
+                       float* marginals, int32_t* ent, float* ent_conf, int32_t* n_ent, int32_t* bad, int32_t B,
+                       int32_t S, int32_t C, void* stream);
 /* ---------------------------------------------------------------------------------------------------------------
  * Chunk-level scoring of a dev / test batch (csrc/metrics.hip): the counts behind the reference's accuracy / precision /
  * recall / F1, overall and per entity type -- the per-token loop of My_cross_attention.py:882-903 followed by
