@@ -638,15 +638,22 @@ int icka_lstm_fwd(const float* gates_x, int64_t ldg, const void* w_hh, void* y, 
 int icka_lstm_bwd(const void* dy, const void* w_hh_t, const void* act, const float* c_all, void* dgates, int64_t ldg,
                   float* dc_carry, int32_t B, int32_t S, int32_t H, int32_t flags, void* stream);
 /* flags of icka_lstm_fwd / icka_lstm_bwd (0 = the defaults; per call, no process-wide switch):
- *   default            for B <= 32 and H <= 768 the recurrence is ONE persistent launch per direction pair -- W_hh slices and cell
- *                      state resident in registers; the blocks hand h_t over as flag-in-data 8-byte words polled by the consumers
- *                      (H % 256 == 0 shapes; others use the ticket form): forward broadcasts h_t, backward reduce-scatters bf16
- *                      partial products of dgates_t . W_hh; in the forward a batch of 17..32 rows runs as two independent tiles
- *                      of 16 rows (separate blocks).
+ *   default            for B <= 32 and H <= 1024 (and a grid of H/16 x 2 blocks that fits the device's CUs) the recurrence is ONE
+ *                      persistent launch per direction pair -- W_hh slices and cell state resident in registers; the blocks hand
+ *                      h_t over as flag-in-data 8-byte words polled by the consumers (forward: H % 256 == 0; backward: H % 256 ==
+ *                      0 and one block per batch tile resident; other shapes use the ticket form): forward broadcasts h_t,
+ *                      backward reduce-scatters bf16 partial products of dgates_t . W_hh; in the forward a batch of 17..32 rows
+ *                      runs as two independent tiles of 16 rows (separate blocks) where all of them are co-resident.  Larger B
+ *                      or H take one launch per time step.
  *   ICKA_LSTM_PER_STEP        one launch per time step instead of the persistent launch.
- *   ICKA_LSTM_TICKETS         persistent launch with step tickets + L1 invalidate instead of tagged words (same forward
- *                             results; backward gradients agree to bf16 rounding).
- *   ICKA_LSTM_NO_BATCH_SPLIT  one block per 16 hidden units holds all rows (same results).
+ *   ICKA_LSTM_TICKETS         persistent launch with step tickets + L1 invalidate instead of tagged words.  Forward results
+ *                             agree with the tagged-word form to f32 summation order (one MFMA chain per gate here, four
+ *                             per-wave partial sums there): c_all differs in its last bits and a few y / act elements by one
+ *                             bf16 ulp -- not bitwise equal; backward gradients agree to bf16 rounding (the tagged-word form
+ *                             rounds its partial products to bf16).  tests/test_lstm_steps_gpu.py holds both to the same
+ *                             per-step bounds.
+ *   ICKA_LSTM_NO_BATCH_SPLIT  one block per 16 hidden units holds all rows (bitwise the same results: a row's arithmetic does
+ *                             not depend on its tile).
  * icka_lstm_barrier_error() returns 1 if a hand-off wait ever gave up (bounded spin: the kernel then finishes with NaN-poisoned
  * data instead of hanging), -1 if the query itself failed. */
 #define ICKA_LSTM_PER_STEP 1

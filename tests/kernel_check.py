@@ -24,6 +24,14 @@ is the eps_fmt |ref| term of the bound; f32 outputs show how much room the accum
                   dbeta 0.001, dbias 0.001; rows of mean 100: y 0.944, xhat 0.302, rstd < 0.001, dres / dx 0.974
     dropout 0.879, gate_bwd du / dcross 0.996, colsum 0.007, features_out fc 0.004; every data-movement kernel bitwise
     token_ce dlogits 0.991 (pad columns zero), loss_sum 0.020; bn_apply y 0.992 (tail rows zero)
+    LSTM, step-wise (tests/lstm_check.py), worst over the cases of each form
+      forward       y      c_all    act              backward   dgates_i  dgates_f  dgates_g  dgates_o  dc_carry
+      LL          0.691  < 0.001   0.885             rs          0.988     0.985     0.984     0.899       -
+      ticket      0.685  < 0.001   0.885             ticket      0.950     0.961     0.960     0.851       -
+      per-step    0.691  < 0.001   0.885             per-step    0.961     0.954     0.963     0.861     0.004
+      (y sits at 0.69, not just under 1: its bound carries the 2^-12 allowance of three device functions on top of the
+      bf16 half-ulp, and the kernels' sigmoid / tanh use a small part of it.)  BiLSTM wiring: dW_ih 0.018, dW_hh 0.016,
+      db 0.003, dx 0.896, the same after an accumulating second backward.
 
 No guard band was disturbed and no NaN pad reached a result in any case.  Two terms of the bounds go beyond the plain
 roundoff sums, both named in the docstrings below: the GELU allowance is RELATIVE (1e-4 |gelu|) for z >= 1, as
