@@ -180,8 +180,8 @@ __global__ __launch_bounds__(64) void crf_grad_kernel(const CrfArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------- Viterbi
-// forward pass: back-pointers into s_bp, final scores (+ end) into s_alpha; returns the number of decoded positions - as
-// counted here (step 0 always, then the raw mask)
+// forward pass: back-pointers into s_bp, final scores (+ end) into s_alpha; returns sum(mask) (raw, step 0 included: a mask
+// with mask[b,0] == 0 decodes one tag less than it has on steps, as the package and the C <= 16 kernels do)
 __device__ __forceinline__ int crf_viterbi_lds(const CrfArgs& a, float* s_T, float* s_alpha, unsigned char* s_bp) {
     const int b = blockIdx.x, j = threadIdx.x, C = a.C, S = a.S;
     for (int i = j; i < C * C; i += 64) s_T[i] = a.trans[i];
@@ -201,6 +201,7 @@ __device__ __forceinline__ int crf_viterbi_lds(const CrfArgs& a, float* s_T, flo
             if (act) score = nx;
         }
     }
+    if (a.mask != nullptr && a.mask[(int64_t)b * S] == 0) len -= 1;   // (the package rejects this; stay consistent)
     __syncthreads();   // block = one wave: orders the LDS exchange
     if (j < C) s_alpha[j] = score + a.end[j];
     __syncthreads();   // block = one wave: orders the LDS exchange
@@ -253,6 +254,7 @@ __global__ __launch_bounds__(64) void crf_decode_kernel(const CrfArgs a) {
             if (act) score = nx;
         }
     }
+    if (a.mask != nullptr && a.mask[(int64_t)b * S] == 0) len -= 1;   // (the package rejects this; stay consistent)
     __syncthreads();   // block = one wave: orders the LDS exchange
     if (j < C) s_alpha[j] = score + a.end[j];
     __syncthreads();   // block = one wave: orders the LDS exchange
@@ -740,9 +742,7 @@ struct LdsSteps {
     __device__ __forceinline__ bool on(int t) const { return s[t] != 0; }
 };
 
-// sum over the samples r < b of the path length the decode kernel writes for r: max(positions counted, 1), where a position
-// counts when mask[r][t] != 0 or (FIRST_ON) t == 0  (wave-uniform)
-template <bool FIRST_ON>
+// sum over the samples r < b of the path length the decode kernels write for r: max(sum(mask[r]), 1)  (wave-uniform)
 __device__ __forceinline__ int64_t crf_flat_offset(const CrfArgs& a, int b, int lane) {
     if (a.mask == nullptr) return (int64_t)b * a.S;
     int64_t off = 0;
@@ -751,17 +751,16 @@ __device__ __forceinline__ int64_t crf_flat_offset(const CrfArgs& a, int b, int 
         int n = 0;
         for (int t0 = 0; t0 < a.S; t0 += 64) {
             const int t = t0 + lane;
-            n += __popcll(__ballot(t < a.S && ((FIRST_ON && t == 0) || mr[t] != 0)));
+            n += __popcll(__ballot(t < a.S && mr[t] != 0));
         }
         off += n > 0 ? n : 1;
     }
     return off;
 }
 
-template <bool FIRST_ON>
 __device__ __forceinline__ void crf_write_flat(const CrfFlatArgs& d, const float* s_fin, const unsigned char* s_bp, int len) {
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int64_t off = crf_flat_offset<FIRST_ON>(d.a, b, lane);
+    const int64_t off = crf_flat_offset(d.a, b, lane);
     if (lane == 0) {
         d.lens[b] = len > 0 ? len : 1;
         crf_backtrace<false>(d.a, s_fin, s_bp, len, d.flat, off, nullptr);
@@ -777,7 +776,7 @@ __global__ __launch_bounds__(64) void crf_score_decode_kernel(const CrfFlatArgs 
         __syncthreads();
     }
     const int len = crf_viterbi_lds(d.a, s_T, s_alpha, s_bp);
-    crf_write_flat<true>(d, s_alpha, s_bp, len);
+    crf_write_flat(d, s_alpha, s_bp, len);
 }
 
 __global__ __launch_bounds__(64) void crf_score_decode_small_kernel(const CrfFlatArgs d) {
@@ -795,7 +794,7 @@ __global__ __launch_bounds__(64) void crf_score_decode_small_kernel(const CrfFla
     }
     __syncthreads();
     const int len = crf_viterbi_small(a, s_bp, s_e, s_on, s_fin);
-    crf_write_flat<false>(d, s_fin, s_bp, len);
+    crf_write_flat(d, s_fin, s_bp, len);
 }
 
 inline bool crf_small(int S, int C) { return C <= CM && S <= 64 * MAXW; }

@@ -543,7 +543,19 @@ int icka_scalar_ratio(float* out, const float* num, const float* den, void* stre
  *   icka_crf_llh   : llh[b] = score(gold path) - log Z
  *   icka_crf_grad  : d_emissions[b,t,:] = gllh[b] * d llh / d e  (written), d_start / d_end / d_trans += (atomics)
  *   icka_crf_decode: Viterbi path per sample, best_tags [B,S] (-1 past sum(mask)), best_score [B] (nullable)
- * icka_crf_grad and icka_crf_decode keep S*C values per sample in LDS: S*C <= 12288. */
+ * icka_crf_grad and icka_crf_decode keep S*C values per sample in LDS: S*C <= 12288 (else ICKA_E_SHAPE, nothing written).
+ * Masks with holes follow the package rule by rule: the recursions advance at position 0 and where mask != 0 (the ON
+ * positions); the gold path takes the transition into an on position t from the label at the LITERAL previous position
+ * t - 1, and its end transition from the label at INDEX sum(mask[b]) - 1; back-pointers are recorded at every step and the
+ * path is read back from index sum(mask[b]) - 1.
+ * mask[b,0] == 0 (the package rejects it): position 0 still takes part in every recursion, but sum(mask[b]) does not count
+ * it, so the end transition is read one position earlier and the decoded path is one tag shorter than there are on
+ * positions: sum(mask[b]) tags, for every C.  A row whose mask is all zero decodes ONE tag and reads its end transition at
+ * position 0.
+ * Labels are clamped into [0, C-1] wherever they are read, so positions that are off may carry pad labels such as -100: a
+ * label that no rule above reads changes nothing, one that is read counts as the clamped value.
+ * d_emissions holds exact +0.0 in all C columns of every off position (every row of the sample is written; the ldd - C pad
+ * columns are not touched). */
 int icka_crf_llh(const float* emissions, int64_t ld, const int64_t* tags, const int64_t* mask, const float* start,
                  const float* end, const float* trans, float* llh, int32_t B, int32_t S, int32_t C, void* stream);
 int icka_crf_grad(const float* emissions, int64_t ld, const int64_t* tags, const int64_t* mask, const float* start,

@@ -32,6 +32,15 @@ is the eps_fmt |ref| term of the bound; f32 outputs show how much room the accum
       (y sits at 0.69, not just under 1: its bound carries the 2^-12 allowance of three device functions on top of the
       bf16 half-ulp, and the kernels' sigmoid / tanh use a small part of it.)  BiLSTM wiring: dW_ih 0.018, dW_hh 0.016,
       db 0.003, dx 0.896, the same after an accumulating second backward.
+    CRF (tests/crf_check.py), against the float64 oracle, worst over the cases of each form ("mixed": the samples of the
+    case took different forms; "either": the scaled form within 2^10 of giving up)
+                          llh     de    d_start  d_end  d_trans             best_score / path
+      scaled             0.059  0.312   0.059   0.078   0.037     small, staged     0.076
+      log domain         0.090  0.627   0.090   0.062   0.064     small, unstaged   0.004
+      mixed / either     0.009  0.000   0.030   0.031   0.023     LDS (C > 16)      0.054
+      (worst-case bounds that grow with the chain: at 315 .. 512 positions every ratio is below 0.03; the 0.627 is a
+      marginal of 1.1e-38 that the device flushes to zero, against the 2^-126 the bound grants for that.  Every integer case
+      gave the exact path and score of the tie-rule reference.)
 
 No guard band was disturbed and no NaN pad reached a result in any case.  Two terms of the bounds go beyond the plain
 roundoff sums, both named in the docstrings below: the GELU allowance is RELATIVE (1e-4 |gelu|) for z >= 1, as
@@ -64,10 +73,12 @@ GUARD_ROWS = 128
 EPS = {BF16: 2.0 ** -8, F16: 2.0 ** -11, F32: 2.0 ** -24}
 U_ACC = 2.0 ** -23
 
-_INT = {BF16: torch.int16, F16: torch.int16, F32: torch.int32, torch.uint8: torch.uint8, torch.int32: torch.int32}
+_INT = {BF16: torch.int16, F16: torch.int16, F32: torch.int32, torch.uint8: torch.uint8, torch.int32: torch.int32,
+        torch.int64: torch.int64}
 # guard patterns (as the signed integer of the element's width).  SENTINEL: outputs; NAN_FILL: inputs.  Both are NaNs in
 # every float format here, both differ from the canonical NaN a kernel could produce (0x7fc0 / 0x7e00 / 0x7fc00000).
-SENTINEL = {BF16: 0x7FA5, F16: 0x7DA5, F32: 0x7FA5A5A5, torch.uint8: 0xA5, torch.int32: 0x5A5A5A5A}
+SENTINEL = {BF16: 0x7FA5, F16: 0x7DA5, F32: 0x7FA5A5A5, torch.uint8: 0xA5, torch.int32: 0x5A5A5A5A,
+            torch.int64: 0x5A5A5A5A5A5A5A5A}
 NAN_FILL = {BF16: 0x7FC1, F16: 0x7E01, F32: 0x7FC00001}
 
 
