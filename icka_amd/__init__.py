@@ -10,7 +10,7 @@ from .modeling import (BertAttention, BertCoAttention, BertCrossAttention, BertC
                        BertSelfOutput, MTCCMBertForMMTokenClassificationCRF, cls_layer_both, scalar_gate_fusion,
                        resolved_precision, set_precision, token_ce_loss)
 from .arena import ParamArena
-from .crf import CRF
+from .crf import CRF, NBestPaths
 from .lstm import BiLSTM
 from .modeling import MTCCMBertForMMTokenClassificationCRF_gate_1
 from .dp import GradReducer
@@ -23,7 +23,7 @@ from . import packing
 from .packing import PackOverflowError, TokenBudgetBatchSampler, set_packed
 from . import metrics
 from .metrics import ChunkEvaluator
-from .entities import EntityDecoder
+from .entities import EntityDecoder, NBestEntities
 from .attention_maps import attention_maps   # (the name now denotes the recorder; the module stays importable by its path)
 
 __all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "BertConfig", "BertModel", "BertEmbeddings", "BertEncoder", "BertLayer", "BertLayerNorm", "BertPooler",
@@ -32,4 +32,5 @@ __all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "Bert
            "BertPreTrainedModel", "MTCCMBertForMMTokenClassificationCRF", "cls_layer_both", "scalar_gate_fusion",
            "token_ce_loss", "set_precision", "resolved_precision", "ParamArena", "cross_modal", "PromptRobertaModel",
            "GradReducer", "graph", "DevicePrefetcher", "GraphedModule", "GraphedStep", "TrainStep", "packing", "set_packed",
-           "PackOverflowError", "TokenBudgetBatchSampler", "metrics", "ChunkEvaluator", "EntityDecoder", "attention_maps"]
+           "PackOverflowError", "TokenBudgetBatchSampler", "metrics", "ChunkEvaluator", "EntityDecoder", "attention_maps",
+           "NBestPaths", "NBestEntities"]

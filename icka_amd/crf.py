@@ -238,6 +238,26 @@ class CRF(ArenaModule):
         rows = best.cpu().tolist()
         return [[v for v in r if v >= 0] for r in rows]
 
+    def decode_nbest(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None, nbest: int = 1) -> "NBestPaths":
+        """The ``nbest`` most likely tag sequences per sample, best first (``icka_crf_nbest``; the definitions and the tie rule
+        are written out in include/icka_hip.h): one launch, no host sync, capturable in a graph.  A path has one tag per
+        on-position (position 0 and the positions with ``mask != 0``); a sample with fewer than ``nbest`` distinct paths
+        (``num_tags ** L``) reports that many in ``n_paths``.  Rank 0 is ``decode``'s path.  Detached.  Limits:
+        ``num_tags <= 16``, ``1 <= nbest <= 8``, ``S <= 512``, ``B <= 2048``, ``S * num_tags * nbest <= 49152``.  Exact
+        log-probabilities of the ranks take ``log_z`` from a second launch: ``out.log_probs(crf.posterior(...).log_z)``, or
+        ``crf.posterior(emissions, out.rank(r), mask).seq_logp`` per rank."""
+        e, _, m = self._prep(emissions.detach(), None, mask)
+        self._arena()
+        B, S, _ = e.shape
+        if isinstance(nbest, bool) or not isinstance(nbest, int):
+            raise ValueError("CRF.decode_nbest: nbest must be an int, got %s" % type(nbest).__name__)
+        if not 1 <= nbest <= K.CRF_NBEST_MAX_K:     # before the buffers are sized by it
+            raise ValueError("CRF.decode_nbest: 1 <= nbest <= %d, got %d" % (K.CRF_NBEST_MAX_K, nbest))
+        out = NBestPaths(B, S, nbest, e.device)
+        K.crf_nbest(e, m, self.start_transitions.detach(), self.end_transitions.detach(), self.transitions.detach(), nbest,
+                    out.lens, out.n_paths, out.scores, out.tags)
+        return out
+
     # ------------------------------------------------------------------------------------------------- posteriors
     def marginals(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``P(y_t = j | emissions)``, f32 in the layout of ``emissions`` ([B,S,C], or [S,B,C] without ``batch_first``): the
@@ -361,6 +381,10 @@ class CrfPosterior(object):
         h = self.joint.cpu()
         if self.tags.deferred_check is not None:
             self.tags.deferred_check()
+        return self.unpack(h)
+
+    def unpack(self, h: torch.Tensor) -> dict:
+        """``host()`` of a host copy ``h`` of ``joint`` the caller made (as part of a larger copy)."""
         out = {}
         for name, (a, b) in self.slices.items():
             out[name] = (h[a:b].view(F32) if name in ("log_z", "seq_logp", "token_conf", "ent_conf") else h[a:b]).tolist()
@@ -370,3 +394,73 @@ class CrfPosterior(object):
     def __repr__(self) -> str:
         return "CrfPosterior(batch=%d, capacity=%d, entities=%s, device=%s)" % (
             self.batch_size, self.capacity, self.ent is not None, self.joint.device)
+
+
+class NBestPaths(object):
+    """The outputs of ``CRF.decode_nbest`` on the device, in ONE buffer (``joint``, int32 words; ``scores`` is an f32 view of
+    it) so that ``host()`` is one device-to-host copy:
+
+        lens int32 [B] | n_paths int32 [B] | scores f32 [B, nbest] | tags int32 [nbest, B*S]
+
+    ``lens[b]`` is the length of every path of sample b, ``n_paths[b]`` how many ranks it has (``min(nbest, num_tags ** L)``),
+    ``scores[b, r]`` the score of rank r (-inf past ``n_paths[b]``, non-increasing in r) and row r of ``tags`` holds rank r of
+    all samples back to back, sample b at ``sum(lens[:b])`` (-1 at the ranks a sample does not have): ``rank(r)`` is a
+    ``DeviceTags`` view of it."""
+
+    def __init__(self, B: int, S: int, nbest: int, device):
+        cap = B * S
+        sizes = [("lens", B), ("n_paths", B), ("scores", B * nbest), ("tags", nbest * cap)]
+        self.slices, o = {}, 0
+        for name, n in sizes:
+            self.slices[name] = (o, o + n)
+            o += n
+        self.joint = torch.empty(o, dtype=torch.int32, device=device)
+        part = lambda name: self.joint[self.slices[name][0]:self.slices[name][1]]
+        self.batch_size, self.capacity, self.nbest = B, cap, nbest
+        self.lens, self.n_paths = part("lens"), part("n_paths")
+        self.scores = part("scores").view(F32).view(B, nbest)
+        self.tags = part("tags").view(nbest, cap)
+
+    def rank(self, r: int) -> DeviceTags:
+        """Rank ``r`` of every sample as a ``DeviceTags`` (a view: no copy), which ``CRF.posterior(paths=...)`` and
+        ``metrics.ChunkEvaluator`` take as it is.  A sample with ``n_paths[b] <= r`` holds -1 there (the posterior kernel
+        refuses such a path and counts it in ``bad``)."""
+        if not 0 <= r < self.nbest:
+            raise IndexError("rank %d of %d" % (r, self.nbest))
+        return DeviceTags(self.lens, self.tags[r])
+
+    def log_probs(self, log_z: torch.Tensor) -> torch.Tensor:
+        """``scores - log_z[:, None]`` on the device, f32 [B, nbest]: the log-probability of every rank (-inf at the ranks a
+        sample does not have), given ``log_z`` of the same emissions and mask (``CRF.posterior(...).log_z``)."""
+        if tuple(log_z.shape) != (self.batch_size,):
+            raise ValueError("log_z must have shape (%d,), got %s" % (self.batch_size, tuple(log_z.shape)))
+        return self.scores - log_z.to(F32)[:, None]
+
+    def unpack(self, h: torch.Tensor) -> dict:
+        """``host()`` of a host copy ``h`` of ``joint`` the caller made (as part of a larger copy)."""
+        part = lambda name: h[self.slices[name][0]:self.slices[name][1]]
+        return {"lens": part("lens").tolist(), "n_paths": part("n_paths").tolist(),
+                "scores": part("scores").view(F32).view(self.batch_size, self.nbest).tolist(),
+                "tags": part("tags").view(self.nbest, self.capacity).tolist()}
+
+    def host(self) -> dict:
+        """Everything on the host as python lists keyed by field name (``scores`` and ``tags`` nested by row): the one
+        device-to-host copy (a host sync)."""
+        return self.unpack(self.joint.cpu())
+
+    @staticmethod
+    def paths_of(h: dict) -> List[List[tuple]]:
+        """Per sample the list of ``(path, score)`` of its ``n_paths[b]`` ranks from the dict of ``host()``."""
+        out, o = [], 0
+        for b, n in enumerate(h["lens"]):
+            out.append([(h["tags"][r][o:o + n], h["scores"][b][r]) for r in range(h["n_paths"][b])])
+            o += n
+        return out
+
+    def tolist(self) -> List[List[tuple]]:
+        """Per sample a list of ``n_paths[b]`` pairs ``(path, score)``, best first (one device-to-host copy)."""
+        return self.paths_of(self.host())
+
+    def __repr__(self) -> str:
+        return "NBestPaths(batch=%d, nbest=%d, capacity=%d, device=%s)" % (
+            self.batch_size, self.nbest, self.capacity, self.joint.device)

@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import metrics
-from .crf import CRF, CrfPosterior
+from .crf import CRF, CrfPosterior, DeviceTags, NBestPaths
 
 
 class Entities(object):
@@ -79,3 +79,65 @@ class EntityDecoder(object):
     def __call__(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None, paths=None) -> Entities:
         post = self.crf.posterior(emissions, paths, mask, label_table=self.table(emissions.device))
         return Entities(post, self.types)
+
+    def nbest(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None, nbest: int = 1) -> "NBestEntities":
+        """The entities of the ``nbest`` best paths of every sample: one ``CRF.decode_nbest`` launch, then one posterior launch
+        per rank; no host sync until ``NBestEntities.tolist()``.  A sample with fewer than ``nbest`` distinct paths has -1 tags
+        at the ranks it lacks; the posterior kernel is given the sample's rank-0 path there instead (so that it refuses
+        nothing) and ``tolist()`` leaves those ranks out."""
+        paths = self.crf.decode_nbest(emissions, mask, nbest)
+        table = self.table(emissions.device)
+        first = paths.rank(0)
+        posts = []
+        for r in range(nbest):
+            tags = first
+            if r > 0:
+                row = paths.tags[r]
+                tags = DeviceTags(paths.lens, torch.where(row < 0, first.tags_flat, row))
+            posts.append(self.crf.posterior(emissions, tags, mask, label_table=table))
+        return NBestEntities(paths, posts, self.types)
+
+
+class NBestEntities(object):
+    """What ``EntityDecoder.nbest`` returns: ``paths`` (the ``NBestPaths``), ``posteriors`` (one ``CrfPosterior`` per rank:
+    ``posteriors[r].seq_logp`` is the log-probability of rank r) and ``types`` (type names by type id)."""
+
+    def __init__(self, paths: NBestPaths, posteriors: Sequence[CrfPosterior], types: Sequence[str]):
+        self.paths = paths
+        self.posteriors = list(posteriors)
+        self.types = list(types)
+
+    def tolist(self) -> List[List[Tuple[str, int, int, float, Tuple[int, ...]]]]:
+        """Per sample the union over its ranks of the entities, as ``(type_name, start, end, confidence, ranks)``: end
+        exclusive, ``confidence`` the exact posterior of the tag span (as in ``Entities``; it does not depend on the rest of
+        the path, and the value of the lowest rank that holds the span is reported), ``ranks`` the ascending tuple of the
+        ranks whose path holds the entity.  Where ranks spell one entity with different tags (``B-PER I-PER`` and
+        ``I-PER I-PER`` at the start of a path), ``confidence`` is the sum of the posteriors of these spans: the events
+        exclude each other, so it is the probability that the positions carry one of the spellings seen.  Sorted by descending confidence, then ``(start, end, type_name)``.  The only call
+        that syncs the host: every buffer goes over in one copy, the union and the sort run on the host.  Raises ValueError
+        when the posterior kernel refused a sample."""
+        parts = [self.paths.joint] + [p.joint for p in self.posteriors]
+        h = torch.cat(parts).cpu()
+        hp, o = self.paths.unpack(h[:parts[0].numel()]), parts[0].numel()
+        ranks = []
+        for p in self.posteriors:
+            ranks.append(p.unpack(h[o:o + p.joint.numel()]))
+            o += p.joint.numel()
+        bad = sum(hr["bad"] for hr in ranks)
+        if bad != 0:
+            raise ValueError("EntityDecoder.nbest: the posterior kernel refused %d path(s)" % bad)
+        out, off = [], 0
+        for b, n in enumerate(hp["lens"]):
+            found = {}      # (type id, start, end) -> [{span tags: confidence}, ranks]
+            for r in range(hp["n_paths"][b]):
+                hr = ranks[r]
+                for k in range(off, off + hr["n_ent"][b]):
+                    ty, s, e = hr["ent"][3 * k:3 * k + 3]
+                    confs, rs = found.setdefault((ty, s, e), [{}, []])
+                    confs.setdefault(tuple(hp["tags"][r][off + s:off + e]), hr["ent_conf"][k])
+                    rs.append(r)
+            rows = [(self.types[ty], s, e, sum(confs.values()), tuple(rs)) for (ty, s, e), (confs, rs) in found.items()]
+            rows.sort(key=lambda x: (-x[3], x[1], x[2], x[0]))
+            out.append(rows)
+            off += n
+        return out

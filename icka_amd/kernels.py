@@ -1102,6 +1102,60 @@ def crf_posterior(emissions, mask, start, end, trans, log_z, bad, *, lens=None, 
           "icka_crf_posterior")
 
 
+CRF_NBEST_MAX_C, CRF_NBEST_MAX_K, CRF_NBEST_MAX_S, CRF_NBEST_MAX_SCK = 16, 8, 512, 49152
+
+
+def crf_nbest(emissions, mask, start, end, trans, nbest, lens, n_paths, scores, tags_flat):
+    """The ``nbest`` best tag paths of every sample (icka_crf_nbest, include/icka_hip.h): ``lens`` and ``n_paths`` int32 [B],
+    ``scores`` f32 [B, nbest], ``tags_flat`` int32 [nbest, capacity >= B*S] (row r: rank r in the layout of
+    ``crf_score_decode``).  One launch, no host sync.  Every operand is checked on the host (dtype, shape, contiguity, the
+    kernel's limits: ValueError; then the device: TypeError) before anything is launched."""
+    def vec(t, name, dtype, shape):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("crf_nbest: %s must be a contiguous %s tensor of shape %s, got %s %s"
+                             % (name, dtype, shape, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
+        return t
+
+    for n, t in (("emissions", emissions), ("start", start), ("end", end), ("trans", trans)):
+        if not isinstance(t, torch.Tensor) or t.dtype != F32 or not t.is_contiguous():
+            raise ValueError("crf_nbest: %s must be contiguous f32" % n)
+    if emissions.dim() != 3:
+        raise ValueError("crf_nbest: emissions must be [B,S,C], got %s" % (tuple(emissions.shape),))
+    B, S, Cn = emissions.shape
+    if start.numel() != Cn or end.numel() != Cn or tuple(trans.shape) != (Cn, Cn):
+        raise ValueError("crf_nbest: transition parameters do not match num_tags = %d" % Cn)
+    if isinstance(nbest, bool) or not isinstance(nbest, int):
+        raise ValueError("crf_nbest: nbest must be an int, got %s" % type(nbest).__name__)
+    if not 1 <= Cn <= CRF_NBEST_MAX_C:
+        raise ValueError("crf_nbest: 1 <= num_tags <= %d, got %d" % (CRF_NBEST_MAX_C, Cn))
+    if not 1 <= nbest <= CRF_NBEST_MAX_K:
+        raise ValueError("crf_nbest: 1 <= nbest <= %d, got %d" % (CRF_NBEST_MAX_K, nbest))
+    if B < 1 or S < 1 or S > CRF_NBEST_MAX_S or B > CRF_FLAT_MAX_B:
+        raise ValueError("crf_nbest: 1 <= B <= %d and 1 <= S <= %d, got [%d, %d, %d]"
+                         % (CRF_FLAT_MAX_B, CRF_NBEST_MAX_S, B, S, Cn))
+    if S * Cn * nbest > CRF_NBEST_MAX_SCK:
+        raise ValueError("crf_nbest: S * num_tags * nbest <= %d (one back-pointer byte each), got %d * %d * %d = %d"
+                         % (CRF_NBEST_MAX_SCK, S, Cn, nbest, S * Cn * nbest))
+    used = [emissions, start, end, trans, vec(lens, "lens", torch.int32, (B,)), vec(n_paths, "n_paths", torch.int32, (B,)),
+            vec(scores, "scores", F32, (B, nbest))]
+    if mask is not None:
+        used.append(vec(mask, "mask", torch.int64, (B, S)))
+    if not (isinstance(tags_flat, torch.Tensor) and tags_flat.dtype == torch.int32 and tags_flat.is_contiguous()
+            and tags_flat.dim() == 2 and tags_flat.shape[0] == nbest and tags_flat.shape[1] >= B * S):
+        raise ValueError("crf_nbest: tags_flat must be a contiguous int32 tensor of shape (%d, >= %d), got %s %s"
+                         % (nbest, B * S, getattr(tags_flat, "dtype", type(tags_flat).__name__),
+                            tuple(getattr(tags_flat, "shape", ()))))
+    used.append(tags_flat)
+    for t in used:
+        _dev(t, "crf_nbest operand")
+        if t.device != emissions.device:
+            raise ValueError("crf_nbest: operands on %s and %s" % (emissions.device, t.device))
+    check(_lib.load().icka_crf_nbest(emissions.data_ptr(), Cn, _ptr(mask), start.data_ptr(), end.data_ptr(),
+                                     trans.data_ptr(), nbest, lens.data_ptr(), n_paths.data_ptr(), scores.data_ptr(),
+                                     tags_flat.data_ptr(), tags_flat.shape[1], B, S, Cn, _stream()),
+          "icka_crf_nbest")
+
+
 # ------------------------------------------------------------------------------------------------- chunk metrics
 CHUNK_EVAL_MAX_S, CHUNK_EVAL_MAX_IDS, CHUNK_EVAL_MAX_TYPES, CHUNK_EVAL_HEAD = 512, 64, 32, 6
 

@@ -605,6 +605,31 @@ int icka_crf_posterior(const float* emissions, int64_t ld, const int64_t* mask, 
                        const int32_t* label_table, int32_t L_ids, float* log_z, float* seq_logp, float* token_conf,
                        float* marginals, int32_t* ent, float* ent_conf, int32_t* n_ent, int32_t* bad, int32_t B,
                        int32_t S, int32_t C, void* stream);
+/* N-best decoding (csrc/crf_nbest.hip): the nbest = K best tag paths of every sample.  One launch, one wave per sample, no
+ * host sync.  The chain is icka_crf_posterior's: per sample the ON-POSITIONS are position 0 and every t >= 1 with
+ * mask[b,t] != 0 (mask NULL = all on), L their number, x_0 .. x_{L-1} the emission rows at them, and
+ *   score(y) = start[y_0] + x_0[y_0] + sum_{i >= 1} (trans[y_{i-1}, y_i] + x_i[y_i]) + end[y_{L-1}].
+ * Sample b has n_paths[b] = min(K, C^L) results (the minimum is taken stepwise: C^L overflows): the n_paths[b] DISTINCT
+ * paths of highest score, by non-increasing score.  TIE RULE: among paths of equal score the one whose REVERSED tag sequence
+ * (y_{L-1}, y_{L-2}, .., y_0) is lexicographically smaller comes first.  The recurrence gives exactly this order: at every
+ * position and tag equal-scoring candidates are kept in ascending (previous tag, previous rank), and the final selection
+ * prefers ascending (tag, rank).  Rank 0 therefore is the path of icka_crf_score_decode (which takes the first maximum at
+ * both places) whenever mask[b,0] != 0 or mask is NULL.  Emissions and parameters are assumed finite; on non-finite input
+ * the paths mean nothing, but every stored tag is in [0, C) and nothing outside the sample's own segments is touched.
+ * Scores are summed in f32 from left to right: ((start + x_0) + trans) + x_1 .. + end.  Outputs:
+ *   lens int32 [B]           L, the length of every rank's path of the sample
+ *   n_paths int32 [B]
+ *   scores f32 [B, K]        score of rank r; -inf at ranks >= n_paths[b]
+ *   tags_flat int32 [K, capacity], capacity >= B*S: row r holds rank r of all samples in the layout of
+ *                            icka_crf_score_decode (sample b at sum(lens[0 .. b-1]), summed inside the kernel), so
+ *                            (lens, row r) goes to icka_crf_posterior and icka_chunk_eval as it is; -1 at the ranks
+ *                            >= n_paths[b]; entries past sum(lens) of every row are left as they are.
+ * Limits (else ICKA_E_SHAPE, nothing launched): 1 <= C <= 16, 1 <= K <= 8, S <= 512, B <= 2048 and S*C*K <= 49152 (one byte
+ * of back-pointer per (position, tag, rank): previous tag * 8 + previous rank).  A sample the kernel could not serve would
+ * come out as n_paths = 0 with -inf scores and -1 tags; the limits above leave no such sample. */
+int icka_crf_nbest(const float* emissions, int64_t ld, const int64_t* mask, const float* start, const float* end,
+                   const float* trans, int32_t nbest, int32_t* lens, int32_t* n_paths, float* scores, int32_t* tags_flat,
+                   int64_t capacity, int32_t B, int32_t S, int32_t C, void* stream);
 /* ---------------------------------------------------------------------------------------------------------------
  * Chunk-level scoring of a dev / test batch (csrc/metrics.hip): the counts behind the reference's accuracy / precision /
  * recall / F1, overall and per entity type -- the per-token loop of My_cross_attention.py:882-903 followed by
