@@ -284,8 +284,8 @@ __global__ __launch_bounds__(256) void token_ce_kernel(const float* __restrict__
     float loss = 0.f, cnt = 0.f;
     if (row < M) {
         const float* p = logits + (int64_t)row * ld;
-        const bool valid = mask[row] != 0;
         const int64_t y = labels[row];
+        const bool valid = mask[row] != 0 && y >= 0 && y < C;   // the row counts (64-bit compare): loss, count AND gradient
         float mx = -INFINITY;
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, p[c]);
         float se = 0.f;
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256) void token_ce_kernel(const float* __restrict__
             if (valid && c < C) gval = expf(p[c] - lse) - (c == (int)y ? 1.f : 0.f);
             d[c] = f2bf(gval);
         }
-        if (valid && y >= 0 && y < C) { loss = lse - p[y]; cnt = 1.f; }
+        if (valid) { loss = lse - p[y]; cnt = 1.f; }
     }
     loss = wave_sum(loss);
     cnt = wave_sum(cnt);
@@ -316,8 +316,8 @@ __global__ __launch_bounds__(256) void token_ce_part_kernel(const float* __restr
     float loss = 0.f, cnt = 0.f;
     if (row < M) {
         const float* p = logits + (int64_t)row * ld;
-        const bool valid = mask[row] != 0;
         const int64_t y = labels[row];
+        const bool valid = mask[row] != 0 && y >= 0 && y < C;   // the row counts (64-bit compare): loss, count AND gradient
         float mx = -INFINITY;
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, p[c]);
         float se = 0.f;
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(256) void token_ce_part_kernel(const float* __restr
             if (dl_f32) reinterpret_cast<float*>(dl_)[(int64_t)row * ldd + c] = gval;
             else reinterpret_cast<bf16_t*>(dl_)[(int64_t)row * ldd + c] = f2bf(gval);
         }
-        if (valid && y >= 0 && y < C) { loss = lse - p[y]; cnt = 1.f; }
+        if (valid) { loss = lse - p[y]; cnt = 1.f; }
     }
     loss = wave_sum(loss);
     cnt = wave_sum(cnt);

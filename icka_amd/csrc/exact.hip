@@ -456,8 +456,8 @@ __global__ __launch_bounds__(256) void xtoken_ce_kernel(const float* __restrict_
     float loss = 0.f, cnt = 0.f;
     if (row < M) {
         const float* p = logits + (int64_t)row * ld;
-        const bool valid = mask[row] != 0;
         const int64_t y = labels[row];
+        const bool valid = mask[row] != 0 && y >= 0 && y < C;   // the row counts (64-bit compare): loss, count AND gradient
         float mx = -INFINITY;
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, p[c]);
         float se = 0.f;
@@ -465,7 +465,7 @@ __global__ __launch_bounds__(256) void xtoken_ce_kernel(const float* __restrict_
         const float lse = mx + logf(se);
         for (int c = 0; c < C; ++c)
             dl[(int64_t)row * C + c] = valid ? expf(p[c] - lse) - (c == (int)y ? 1.f : 0.f) : 0.f;
-        if (valid && y >= 0 && y < C) { loss = lse - p[y]; cnt = 1.f; }
+        if (valid) { loss = lse - p[y]; cnt = 1.f; }
     }
     loss = wave_sum(loss);
     cnt = wave_sum(cnt);

@@ -517,7 +517,11 @@ int icka_relu_bwd(const void* dy, const void* y, void* dx, int64_t n, int32_t is
 int icka_sample_swap(const void* x, void* y, int32_t B, int64_t sample_bytes, int32_t n_neg, void* stream);
 /* Token-level cross-entropy over valid tokens (benchmark loss), fused forward + backward:
  * logits f32 [M,C] (ld), labels/mask int64 [M]; loss_sum f32[1] += sum of -log p ; count f32[1] += #valid ;
- * dlogits bf16 [M, ldd] (ldd >= C, pad columns zeroed) = (softmax - onehot) * valid  (see icka_scale_by_ratio). */
+ * dlogits bf16 [M, ldd] (ldd >= C, pad columns zeroed) = (softmax - onehot) * valid  (see icka_scale_by_ratio).
+ * A row COUNTS ("valid") if and only if mask != 0 and 0 <= label < C, compared in 64 bits (a label of -100, C or
+ * 2^32 + c does not count, as with CrossEntropyLoss(ignore_index=...)).  A row that does not count contributes nothing
+ * to loss_sum / count and its gradient row is all zeros.  The same rule holds for icka_token_ce_fused and
+ * icka_x_token_ce. */
 int icka_token_ce(const float* logits, int64_t ld, const int64_t* labels, const int64_t* mask, float* loss_sum,
                   float* count, void* dlogits, int64_t ldd, int32_t M, int32_t C, void* stream);
 /* y = x * num[0] / max(den[0], 1) for bf16 [n] with DEVICE scalars (NULL = 1): applies dloss / #valid to the
@@ -526,7 +530,8 @@ int icka_scale_by_ratio(const void* x, void* y, const float* num, const float* d
 /* The same loss without pre-zeroed accumulators and without atomics (fixed summation order, bitwise reproducible):
  * stats f32[3] = {sum of token losses, number of valid tokens, mean loss}; dlogits [M, ldd] unscaled, bf16 or f32
  * (dl_is_f32: autograd wants the gradient of the f32 logits in f32); partials = f32 workspace of
- * icka_token_ce_workspace_floats(M).  Two launches (per-block partials, finalize). */
+ * icka_token_ce_workspace_floats(M).  Two launches (per-block partials, finalize).  Which rows count: as for
+ * icka_token_ce (mask != 0 and 0 <= label < C in 64 bits; every other row has an all-zero gradient row). */
 int64_t icka_token_ce_workspace_floats(int32_t M);
 int icka_token_ce_fused(const float* logits, int64_t ld, const int64_t* labels, const int64_t* mask, float* stats,
                         float* partials, void* dlogits, int64_t ldd, int32_t dl_is_f32, int32_t M, int32_t C, void* stream);
@@ -874,7 +879,9 @@ int icka_x_embed_prompt_fwd(const int64_t* ids, const int32_t* src, const float*
 int icka_x_embed_prompt_scatter(const float* dpre, const int64_t* ids, const int32_t* src, float* dword, float* dpos,
                                 float* dtyp, float* dprompt, int32_t B, int32_t S_in, int32_t S, int32_t P, int32_t H,
                                 int32_t pos_offset, int32_t padding_idx, void* stream);
-/* f32 twins of icka_token_ce / icka_scale_by_ratio (dlogits f32 [M,C] contiguous, unscaled) */
+/* f32 twins of icka_token_ce / icka_scale_by_ratio (dlogits f32 [M,C] contiguous, unscaled).  A row counts if and only if
+ * mask != 0 and 0 <= label < C in 64 bits; a row that does not count adds nothing to loss_sum / count and has an all-zero
+ * gradient row. */
 int icka_x_token_ce(const float* logits, int64_t ld, const int64_t* labels, const int64_t* mask, float* loss_sum,
                     float* count, float* dlogits, int32_t M, int32_t C, void* stream);
 int icka_x_scale_by_ratio(const float* x, float* y, const float* num, const float* den, int64_t n, void* stream);

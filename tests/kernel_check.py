@@ -41,6 +41,21 @@ is the eps_fmt |ref| term of the bound; f32 outputs show how much room the accum
       (worst-case bounds that grow with the chain: at 315 .. 512 positions every ratio is below 0.03; the 0.627 is a
       marginal of 1.1e-38 that the device flushes to zero, against the 2^-126 the bound grants for that.  Every integer case
       gave the exact path and score of the tie-rule reference.)
+    fp32-exact (tests/exact_check.py), worst over the cases and both stride variants of each kernel
+      x_gemm        C 0.299 (all four ops, K = 1 .. 50), batched 0.055; the gaps between batch slices untouched
+      x_ln          y 0.135, xhat 0.059, rstd 0.057, dpre 0.135, ddense 0.126; rows of mean 100: y 0.003, dpre 0.015
+      x_colsum      0.233
+      x_embed       y 0.074, xhat 0.057, rstd 0.030; scatter dword 0.111, dpos 0.115, dtyp 0.090 (padding row bitwise)
+      x_embed_prompt  y 0.099, xhat 0.057, rstd 0.055; scatter dword 0.112, dpos 0.122, dtyp 0.053 (dprompt bitwise)
+      x_softmax     P 0.061, Pd 0.065, dS 0.155; a batch with every key at -10000: P / Pd 0.796
+      x_act         gelu y 0.453, dx 0.654; tanh y 0.469, dx 0.492; gate y 0.596, y2 0.497, dx 0.696, dx2 0.999
+      x_dropout 0.978, x_add 1.000, x_scale_by_ratio 0.595 (one or two roundings: the bound IS the half ulp);
+      x_concat2 and x_regions_to_tokens bitwise
+      x_sample_gate out 0.386, da 0.378, dc 0.437, dgate 0.117 (mode 1: the two words -t and +t bitwise)
+      x_lstm_cell   act 0.471, c 0.367, y 0.248, dgates 0.386, dc_carry 0.445 (hprev bitwise the neighbouring y row)
+      x_token_ce    dlogits 0.162, loss_sum 0.015, count exact (labels -100, C and 2^32 + 3 on valid rows: zero rows);
+                    the fused form: dlogits 0.991 (bf16) / 0.162 (f32), loss sum and mean 0.016
+      (the device's expf / logf / erff / tanhf meet the 2^-22 the bounds require of them: no replacement was needed.)
 
 No guard band was disturbed and no NaN pad reached a result in any case.  Two terms of the bounds go beyond the plain
 roundoff sums, both named in the docstrings below: the GELU allowance is RELATIVE (1e-4 |gelu|) for z >= 1, as

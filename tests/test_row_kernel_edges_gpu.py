@@ -188,47 +188,84 @@ def test_cast_pad_zeroes_its_pad_columns_and_nothing_else(M, lds):
     g.check(tail_cols=ldd - N, expect=0, what="cast_pad dst")
 
 
-@pytest.mark.parametrize("C,ldd,ld", [(13, 16, 13), (13, 16, 16), (9, 16, 12), (8, 8, 8)])
-@pytest.mark.parametrize("M", [1, 5, 130, 300])
-def test_token_ce_zeroes_its_pad_columns_and_nothing_else(M, C, ldd, ld):
-    """icka_token_ce: dlogits bf16 [M, ldd] = (softmax - onehot) * valid on the C logical columns, ZEROS in the pad columns
-    [C, ldd) of every row; loss_sum / count accumulate over the valid rows.  M = 300 takes two blocks.
+def _token_ce_case(M, C):
+    """logits, labels, mask and the float64 reference of a token-CE case.  A row COUNTS iff mask != 0 and 0 <= label < C in 64
+    bits (include/icka_hip.h); the first valid rows (up to three, never the last one) carry the labels -100, C and 2^32 + 3,
+    which do not count: their gradient rows are zero and they add nothing to the loss or the count.
 
     Bound of a gradient element (p = softmax probability, x the f32 logits, exact as given):  the exponent x_c - lse carries
     u (|x_c| + |lse|) from the subtraction and the error of lse -- u |mx| for max + log, 2 u for logf, (C + 4) u relative
     for the f32 sum of C exponentials, each of which has the 2 u of expf and u |x_c - mx| <= u (|x_c| + |mx|) in its own
     exponent (|mx| <= |lse| + log C).  Together  D_c = u (2 |x_c| + 3 |lse| + 3 log C + C + 8), and
-    e_g = p expm1(D_c) + 2 u p (expf) + u |g| (the onehot subtraction), then the bf16 store.  The loss of a row is
-    lse - x_y: D_y + u |loss|; loss_sum adds the rows in any order: (M + 4) u sum|loss|."""
-    k = _k()
+    e_g = p expm1(D_c) + 2 u p (expf) + u |g| (the onehot subtraction), then the store.  The loss of a row is
+    lse - x_y: D_y + u |loss|; the sum adds the rows in any order: (M + 4) u sum|loss|."""
     x0 = _rnd(M, C, seed=1, scale=3.0).to(F32)
     labels0 = torch.randint(0, C, (M,), generator=torch.Generator().manual_seed(2))
     mask0 = (torch.arange(M) % 3 != 1).long()
     mask0[0] = 1
-    logits = kc.guarded_input(x0, ld=ld)
-    g = kc.Guarded(M, C, BF16, ld=ldd)
-    dl = g.flat.as_strided((M, ldd), (ldd, 1), g.start)
-    (acc, c_acc) = kc.guarded(1, 2, F32, init=torch.tensor([[0.5, 2.0]]))
-    k.token_ce(logits, labels0.cuda(), mask0.cuda(), acc[0, 0:1], acc[0, 1:2], dl)
+    rows = torch.nonzero(mask0)[:, 0].tolist()
+    for row, lab in zip(rows[:len(rows) - 1], (-100, C, 2 ** 32 + 3)):      # (the last valid row always stays in range)
+        labels0[row] = lab
+    counts0 = (mask0 != 0) & (labels0 >= 0) & (labels0 < C)
     x = x0.double().cuda()
     lse = torch.logsumexp(x, -1, keepdim=True)
     p = torch.exp(x - lse)
-    valid = mask0.double().cuda()[:, None]
-    onehot = torch.nn.functional.one_hot(labels0, C).double().cuda()
+    valid = counts0.double().cuda()[:, None]
+    onehot = torch.nn.functional.one_hot(torch.where(counts0, labels0, torch.zeros_like(labels0)), C).double().cuda() * valid
     ref = (p - onehot) * valid
     D = kc.U_ACC * (2 * x.abs() + 3 * lse.abs() + 3 * math.log(C) + C + 8)
     e = (p * torch.expm1(D) + 2 * kc.U_ACC * p + kc.U_ACC * ref.abs()) * valid
-    kc.assert_within(g.view, ref, kc.stored(e, ref, BF16), "token_ce dlogits")
-    g.check(tail_cols=ldd - C, expect=0, what="token_ce dlogits")
     loss = (lse - (x * onehot).sum(-1, keepdim=True)) * valid
     e_loss = ((D * onehot).sum(-1, keepdim=True) + kc.U_ACC * loss.abs()) * valid
-    ref_sum, e_sum = kc.with_beta(e_loss.sum() + (M + 4) * kc.U_ACC * loss.abs().sum(), loss.sum(), 1.0,
-                                  torch.tensor(0.5, dtype=torch.float64, device="cuda"))
+    return dict(x0=x0, labels0=labels0, mask0=mask0, n=int(counts0.sum()), ref=ref, e=e, loss_sum=loss.sum(),
+                e_sum=e_loss.sum() + (M + 4) * kc.U_ACC * loss.abs().sum())
+
+
+@pytest.mark.parametrize("C,ldd,ld", [(13, 16, 13), (13, 16, 16), (9, 16, 12), (8, 8, 8)])
+@pytest.mark.parametrize("M", [1, 5, 130, 300])
+def test_token_ce_zeroes_its_pad_columns_and_nothing_else(M, C, ldd, ld):
+    """icka_token_ce: dlogits bf16 [M, ldd] = (softmax - onehot) * valid on the C logical columns, ZEROS in the pad columns
+    [C, ldd) of every row; loss_sum / count accumulate over the rows that count (``_token_ce_case``).  M = 300 takes two
+    blocks."""
+    k = _k()
+    t = _token_ce_case(M, C)
+    logits = kc.guarded_input(t["x0"], ld=ld)
+    g = kc.Guarded(M, C, BF16, ld=ldd)
+    dl = g.flat.as_strided((M, ldd), (ldd, 1), g.start)
+    (acc, c_acc) = kc.guarded(1, 2, F32, init=torch.tensor([[0.5, 2.0]]))
+    k.token_ce(logits, t["labels0"].cuda(), t["mask0"].cuda(), acc[0, 0:1], acc[0, 1:2], dl)
+    kc.assert_within(g.view, t["ref"], kc.stored(t["e"], t["ref"], BF16), "token_ce dlogits")
+    g.check(tail_cols=ldd - C, expect=0, what="token_ce dlogits")
+    ref_sum, e_sum = kc.with_beta(t["e_sum"], t["loss_sum"], 1.0, torch.tensor(0.5, dtype=torch.float64, device="cuda"))
     ref_sum, e_sum = ref_sum.reshape(1), e_sum.reshape(1)
     kc.assert_within(acc[0, 0:1], ref_sum, kc.stored(e_sum, ref_sum, F32), "token_ce loss_sum")
-    assert float(acc[0, 1]) == 2.0 + float(mask0.sum())
+    assert float(acc[0, 1]) == 2.0 + t["n"]
     c_acc(what="token_ce accumulators")
     kc.report("token_ce M=%d C=%d ldd=%d ld=%d" % (M, C, ldd, ld))
+
+
+@pytest.mark.parametrize("dt", [BF16, F32])
+@pytest.mark.parametrize("M", [5, 300])
+def test_token_ce_fused_counts_the_same_rows(M, dt):
+    """icka_token_ce_fused (per-block partials, fixed order): stats = {loss sum, rows that count, mean}; the gradient rows of
+    the rows that do not count -- masked out, or a label outside [0, C) on a valid row -- are zero, pad columns too."""
+    k = _k()
+    C, ldd, ld = 13, 16, 16
+    t = _token_ce_case(M, C)
+    logits = kc.guarded_input(t["x0"], ld=ld)
+    g = kc.Guarded(M, C, dt, ld=ldd)
+    dl = g.flat.as_strided((M, ldd), (ldd, 1), g.start)
+    stats, c_stats = kc.guarded(1, 3, F32)
+    k.token_ce_fused(logits, t["labels0"].cuda(), t["mask0"].cuda(), stats[0], dl)
+    kc.assert_within(g.view, t["ref"], kc.stored(t["e"], t["ref"], dt), "token_ce_fused dlogits")
+    g.check(tail_cols=ldd - C, expect=0, what="token_ce_fused dlogits")
+    ref_sum, e_sum = t["loss_sum"].reshape(1), kc.stored(t["e_sum"], t["loss_sum"], F32).reshape(1)
+    kc.assert_within(stats[0, 0:1], ref_sum, e_sum, "token_ce_fused loss sum")
+    assert float(stats[0, 1]) == t["n"]
+    ref_mean = ref_sum / max(t["n"], 1)               # one more rounding: the division
+    kc.assert_within(stats[0, 2:3], ref_mean, kc.stored(e_sum / max(t["n"], 1), ref_mean, F32), "token_ce_fused mean")
+    c_stats(what="token_ce_fused stats")
+    kc.report("token_ce_fused M=%d %s" % (M, str(dt)[6:]))
 
 
 @pytest.mark.parametrize("n", [1, 7, 8, 1000003])
