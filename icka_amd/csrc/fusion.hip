@@ -511,7 +511,9 @@ extern "C" int64_t icka_cls_head_slab_floats(int32_t H, int32_t C) { return (int
 static int cls_head_fwd_impl(bool f16, const void* seq, const void* gated, const void* W, const float* bias, float* logits,
                              int32_t M, int32_t H, int32_t C, void* stream) {
     if (!seq || !gated || !W || !logits) return ICKA_E_ARG;
-    if (M <= 0 || H <= 0 || H % 8 || C <= 0 || C > CLS_MAXC || (int64_t)C * 2 * H * 2 > 44 * 1024) return ICKA_E_SHAPE;
+    // a lane covers the chunks lane + 64 i, i < 4, of [seq | gated]: 2H/8 <= 256
+    if (M <= 0 || H <= 0 || H % 8 || C <= 0 || C > CLS_MAXC || 2 * H / 8 > 256 || (int64_t)C * 2 * H * 2 > 44 * 1024)
+        return ICKA_E_SHAPE;
     if ((reinterpret_cast<uintptr_t>(seq) | reinterpret_cast<uintptr_t>(gated) | reinterpret_cast<uintptr_t>(W)) & 15)
         return ICKA_E_ALIGN;
     int grid = (M + 7) / 8;   // 4 waves x 2 rows per pass

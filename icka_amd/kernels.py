@@ -292,6 +292,8 @@ def cls_head_fwd(seq, gated, W, bias, logits):
         raise ValueError("cls_head_fwd: contiguous operands")
     if W.dtype != dt or tuple(W.shape) != (Cn, 2 * H) or logits.dtype != F32 or tuple(logits.shape) != (M, Cn):
         raise ValueError("cls_head_fwd: W %s [C,2H], logits f32 [M,C]" % dt)
+    if H % 8 or 2 * H // 8 > 256:
+        raise ValueError("cls_head_fwd: H must be a multiple of 8 with 2H/8 <= 256 (H <= 1024), got H=%d" % H)
     lib = _lib.load()
     fn = lib.icka_cls_head_fwd_h if dt == F16 else lib.icka_cls_head_fwd
     check(fn(seq.data_ptr(), gated.data_ptr(), W.data_ptr(), _ptr(bias), logits.data_ptr(), M, H, Cn, _stream()),

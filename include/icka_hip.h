@@ -446,7 +446,8 @@ int icka_gate_bwd(const void* dout, int64_t lddout, const void* g, const void* c
  *        half, the gate backward applied in place: du = dgated*cross*g*(1-g), dcross = dgated*g (as icka_gate_bwd);
  *        dW / db leave as icka_cls_head_bwd_slabs(M) slabs of icka_cls_head_slab_floats(H,C) floats each
  *        ([C*2H] weight part, then [16] bias part), to be summed by icka_gemm_grouped_ex slab reductions.
- * Needs 2H/8 <= 256 (H <= 1024). */
+ * Needs 2H/8 <= 256 (H <= 1024), in the forward (both forms) as in the backward: anything else returns ICKA_E_SHAPE
+ * and launches nothing. */
 int icka_cls_head_fwd(const void* seq, const void* gated, const void* W, const float* bias, float* logits, int32_t M,
                       int32_t H, int32_t C, void* stream);
 /* "mixed16" form of icka_cls_head_fwd: seq, gated and W are IEEE fp16 (the fp16 twins of the encoder outputs, the fp16
