@@ -129,6 +129,35 @@ class _CrfFn(torch.autograd.Function):
         return None, de, None, None, None, None
 
 
+class _CrfConstrainedFn(torch.autograd.Function):
+    """``log Z_A - log Z`` per sample (icka_crf_constrained_llh / _grad); the arena gradients are handled as in ``_CrfFn``."""
+
+    @staticmethod
+    def forward(ctx, anchor, emissions, allowed, mask, mod, A: ParamArena):
+        B = emissions.shape[0]
+        out = torch.empty(3, B, dtype=F32, device=emissions.device)      # llh | log Z | log Z_A
+        K.crf_constrained_llh(emissions, mask, allowed, mod.start_transitions, mod.end_transitions, mod.transitions,
+                              out[0], out[1], out[2])
+        ctx.mod, ctx.A = mod, A
+        ctx.save_for_backward(emissions, allowed, mask)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gllh):
+        emissions, allowed, mask = ctx.saved_tensors
+        mod, A = ctx.mod, ctx.A
+        ps = (mod.start_transitions, mod.end_transitions, mod.transitions)
+        if A.grad_beta(ps) == 0.0:          # first write of this accumulation cycle: the kernel adds with atomics
+            for p in ps:
+                A.g(p).zero_()
+        de = torch.empty_like(emissions)
+        K.crf_constrained_grad(emissions, mask, allowed, mod.start_transitions, mod.end_transitions, mod.transitions,
+                               gllh.to(F32).contiguous(), de, A.g(mod.start_transitions), A.g(mod.end_transitions),
+                               A.g(mod.transitions))
+        A.flush_final()
+        return None, de, None, None, None, None
+
+
 class CRF(ArenaModule):
     def __init__(self, num_tags: int, batch_first: bool = False) -> None:
         if num_tags <= 0:
@@ -343,6 +372,149 @@ class CRF(ArenaModule):
         if mg is not None:
             post.marginals = mg if self.batch_first else mg.transpose(0, 1)
         return post
+
+    # ------------------------------------------------------------------------------------------------ constraints
+    @staticmethod
+    def allowed_from_tags(tags: torch.Tensor, num_tags: int, unknown_index: int = -1) -> torch.Tensor:
+        """The allowed sets of partially labelled data, int64 bit sets in the shape of ``tags``: a known tag ``k`` becomes
+        ``1 << k``, ``unknown_index`` becomes "every tag" (the low ``num_tags`` bits; -1 at 64 tags).  Pure torch: works on
+        any device."""
+        if not 1 <= num_tags <= 64:
+            raise ValueError("allowed_from_tags: 1 <= num_tags <= 64, got %d" % num_tags)
+        if not isinstance(tags, torch.Tensor) or tags.is_floating_point() or tags.dtype == torch.bool:
+            raise ValueError("allowed_from_tags: tags must be an integer tensor, got %s"
+                             % getattr(tags, "dtype", type(tags).__name__))
+        t = tags.to(torch.int64)
+        every = -1 if num_tags == 64 else (1 << num_tags) - 1
+        one = torch.ones_like(t) << t.clamp(0, 63)          # 1 << 63 wraps to the sign bit: bit 63
+        known = (t >= 0) & (t < num_tags) & (t != unknown_index)
+        out = torch.where(known, one, torch.zeros_like(t))  # an id that names no tag allows nothing
+        return torch.where(t == unknown_index, torch.full_like(t, every), out)
+
+    @staticmethod
+    def pack_allowed(allowed: torch.Tensor) -> torch.Tensor:
+        """bool / uint8 [..., C] (non-zero = allowed) -> int64 [...] bit sets, bit j = tag j (C <= 64; tag 63 is the sign
+        bit).  Layout work with torch ops on the tensor's own device."""
+        if not isinstance(allowed, torch.Tensor) or allowed.dtype not in (torch.bool, torch.uint8) or allowed.dim() < 1:
+            raise ValueError("pack_allowed: a bool or uint8 [..., C] tensor, got %s %s"
+                             % (getattr(allowed, "dtype", type(allowed).__name__), tuple(getattr(allowed, "shape", ()))))
+        Cn = allowed.shape[-1]
+        if not 1 <= Cn <= 64:
+            raise ValueError("pack_allowed: 1 <= C <= 64, got %d" % Cn)
+        bits = torch.ones(Cn, dtype=torch.int64, device=allowed.device) << torch.arange(Cn, device=allowed.device)
+        return ((allowed != 0).to(torch.int64) * bits).sum(-1)     # distinct bits: the sum is their union (wraps at bit 63)
+
+    def _prep_allowed(self, who: str, emissions, allowed, mask):
+        """The host-side checks of ``allowed`` (before any device check) -> (e, m, int64 [B,S] bit sets), batch-first, with
+        position 0 of the mask forced on."""
+        if not isinstance(allowed, torch.Tensor):
+            raise ValueError("%s: allowed must be a tensor, got %s" % (who, type(allowed).__name__))
+        if isinstance(emissions, torch.Tensor) and emissions.dim() == 3 and emissions.size(2) == self.num_tags:
+            lead = tuple(emissions.shape[:2])
+            if allowed.dtype == torch.int64:
+                want = lead
+            elif allowed.dtype in (torch.bool, torch.uint8):
+                want = lead + (self.num_tags,)
+            else:
+                raise ValueError("%s: allowed must be int64 bit sets %s or bool / uint8 %s, got %s"
+                                 % (who, lead, lead + (self.num_tags,), allowed.dtype))
+            if tuple(allowed.shape) != want:
+                raise ValueError("%s: allowed must have shape %s for %s, got %s"
+                                 % (who, want, allowed.dtype, tuple(allowed.shape)))
+            S = lead[1] if self.batch_first else lead[0]
+            if S * self.num_tags > K.CRF_MAX_SC:
+                raise ValueError("%s: S * num_tags <= %d, got %d * %d = %d"
+                                 % (who, K.CRF_MAX_SC, S, self.num_tags, S * self.num_tags))
+            if allowed.device != emissions.device:
+                raise ValueError("%s: emissions on %s, allowed on %s" % (who, emissions.device, allowed.device))
+        e, _, m = self._prep(emissions, None, mask)
+        if allowed.dtype != torch.int64:
+            allowed = self.pack_allowed(allowed)
+        if not self.batch_first:
+            allowed = allowed.transpose(0, 1)
+        if m is not None:
+            m[:, 0] = 1            # (m is _prep's own copy) position 0 is on, as in posterior
+        return e, m, allowed.contiguous()
+
+    def constrained_llh(self, emissions: torch.Tensor, allowed: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                        reduction: str = "sum") -> torch.Tensor:
+        """The marginal log-likelihood of all tag paths inside per-position allowed sets, ``log Z_A - log Z`` (<= 0): the loss
+        of partially labelled data (``-crf.constrained_llh(...)``).  Differentiable in ``emissions`` and the three
+        parameters.  ``allowed``: int64 bit sets in the layout of the mask (bit j = tag j; ``allowed_from_tags`` builds them
+        from labels with an unknown index), or a bool / uint8 tensor in the layout of the emissions.  The chain runs over
+        position 0 and the positions with ``mask != 0``, as in ``posterior``; reductions as in ``forward``.  A sample with an
+        empty set at one of its positions is infeasible: its value is ``-inf`` (so is a reduction over it) and its gradients
+        are zeros.  No host sync.  The definitions are written out in include/icka_hip.h.  Posteriors, N-best and entity
+        confidences under constraints, transition-level constraint arguments (write -1e4 into ``transitions``) and packed
+        batches are not covered."""
+        if reduction not in ("none", "sum", "mean", "token_mean"):
+            raise ValueError("invalid reduction: %s" % reduction)
+        e, m, al = self._prep_allowed("CRF.constrained_llh", emissions, allowed, mask)
+        A = self._arena()
+        llh = _CrfConstrainedFn.apply(A.anchor, e, al, m, self, A)
+        return self._reduce(llh, m, e, reduction)
+
+    def constrained_decode(self, emissions: torch.Tensor, allowed: torch.Tensor,
+                           mask: Optional[torch.Tensor] = None) -> "ConstrainedPaths":
+        """The most likely tag path inside per-position allowed sets (``allowed`` as in ``constrained_llh``): known tags are
+        forced with singleton sets, excluded ones by clearing their bits.  Ties take the first maximum over the allowed
+        tags, so with every tag allowed the paths are ``decode``'s.  An infeasible sample is reported, never decoded: -1
+        tags, a ``-inf`` score, ``None`` in ``tolist()``, one more in ``infeasible``.  Detached, one launch, no host sync."""
+        e, m, al = self._prep_allowed("CRF.constrained_decode", emissions.detach() if isinstance(emissions, torch.Tensor)
+                                      else emissions, allowed, mask)
+        self._arena()
+        B, S, _ = e.shape
+        if B > K.CRF_FLAT_MAX_B:
+            raise ValueError("CRF.constrained_decode: B <= %d, got %d" % (K.CRF_FLAT_MAX_B, B))
+        out = ConstrainedPaths(B, S, e.device)
+        out.infeasible.zero_()
+        K.crf_constrained_decode(e, m, al, self.start_transitions.detach(), self.end_transitions.detach(),
+                                 self.transitions.detach(), out.tags.lens, out.tags.tags_flat, out.scores, out.infeasible)
+        return out
+
+
+class ConstrainedPaths(object):
+    """The outputs of ``CRF.constrained_decode`` on the device, in ONE buffer (``joint``, int32 words; ``scores`` is an f32
+    view of it) so that ``host()`` is one device-to-host copy:
+
+        infeasible int32 [1] | lens int32 [B] | tags_flat int32 [B*S] | scores f32 [B]
+
+    ``tags`` is a ``DeviceTags`` view of lens + tags_flat, which ``CRF.posterior(paths=...)`` and ``metrics.ChunkEvaluator``
+    take as it is.  An infeasible sample holds -1 in its ``lens[b]`` slots and ``scores[b] = -inf``."""
+
+    def __init__(self, B: int, S: int, device):
+        cap = B * S
+        sizes = [("infeasible", 1), ("lens", B), ("tags_flat", cap), ("scores", B)]
+        self.slices, o = {}, 0
+        for name, n in sizes:
+            self.slices[name] = (o, o + n)
+            o += n
+        self.joint = torch.empty(o, dtype=torch.int32, device=device)
+        part = lambda name: self.joint[self.slices[name][0]:self.slices[name][1]]
+        self.batch_size, self.capacity = B, cap
+        self.infeasible = part("infeasible")
+        self.tags = DeviceTags(part("lens"), part("tags_flat"))
+        self.scores = part("scores").view(F32)
+
+    def unpack(self, h: torch.Tensor) -> dict:
+        """``host()`` of a host copy ``h`` of ``joint`` the caller made (as part of a larger copy)."""
+        part = lambda name: h[self.slices[name][0]:self.slices[name][1]]
+        lens, flat = part("lens").tolist(), part("tags_flat").tolist()
+        paths = [None if (p and p[0] < 0) else p for p in split_tags(lens, flat)]
+        return {"infeasible": int(part("infeasible")[0]), "lens": lens, "scores": part("scores").view(F32).tolist(),
+                "paths": paths}
+
+    def host(self) -> dict:
+        """``infeasible``, ``lens``, ``scores`` and ``paths`` (per sample a list of tags, None for an infeasible sample) on the
+        host: the one device-to-host copy (a host sync)."""
+        return self.unpack(self.joint.cpu())
+
+    def tolist(self) -> List[Optional[List[int]]]:
+        """Per sample its path, or None for an infeasible sample (one device-to-host copy)."""
+        return self.host()["paths"]
+
+    def __repr__(self) -> str:
+        return "ConstrainedPaths(batch=%d, capacity=%d, device=%s)" % (self.batch_size, self.capacity, self.joint.device)
 
 
 class CrfPosterior(object):

@@ -1158,6 +1158,110 @@ def crf_nbest(emissions, mask, start, end, trans, nbest, lens, n_paths, scores, 
           "icka_crf_nbest")
 
 
+def _crf_constrained_check(who, emissions, mask, allowed, start, end, trans, extra, flat_b=False):
+    """The host-side checks shared by the three constrained-CRF entries -> (B, S, C).  ``extra``: (tensor, name, dtype, shape)
+    of the entry's own operands (a None tensor is skipped).  ValueError for dtype / shape / contiguity / the kernel's limits,
+    then TypeError for an operand that is not on the device, before anything is launched."""
+    def vec(t, name, dtype, shape):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("%s: %s must be a contiguous %s tensor of shape %s, got %s %s"
+                             % (who, name, dtype, shape, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
+        return t
+
+    for n, t in (("emissions", emissions), ("start", start), ("end", end), ("trans", trans)):
+        if not isinstance(t, torch.Tensor) or t.dtype != F32 or not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous f32" % (who, n))
+    if emissions.dim() != 3:
+        raise ValueError("%s: emissions must be [B,S,C], got %s" % (who, tuple(emissions.shape)))
+    B, S, Cn = emissions.shape
+    if start.numel() != Cn or end.numel() != Cn or tuple(trans.shape) != (Cn, Cn):
+        raise ValueError("%s: transition parameters do not match num_tags = %d" % (who, Cn))
+    if not 1 <= Cn <= 64:
+        raise ValueError("%s: 1 <= num_tags <= 64 (one lane and one bit per tag), got %d" % (who, Cn))
+    if B < 1 or S < 1:
+        raise ValueError("%s: empty batch [%d, %d, %d]" % (who, B, S, Cn))
+    if S * Cn > CRF_MAX_SC:
+        raise ValueError("%s: S * num_tags <= %d, got %d * %d = %d" % (who, CRF_MAX_SC, S, Cn, S * Cn))
+    if flat_b and B > CRF_FLAT_MAX_B:
+        raise ValueError("%s: B <= %d (the kernel sums the path offsets itself), got %d" % (who, CRF_FLAT_MAX_B, B))
+    used = [emissions, start, end, trans, vec(allowed, "allowed", torch.int64, (B, S))]
+    if mask is not None:
+        used.append(vec(mask, "mask", torch.int64, (B, S)))
+    for t, name, dtype, shape in extra:
+        shape = shape(B, S, Cn) if callable(shape) else shape
+        if t is None:
+            continue
+        if shape[0] == "at least":           # 1-D with room for shape[1] entries
+            if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.dim() == 1
+                    and t.numel() >= shape[1]):
+                raise ValueError("%s: %s must be a contiguous 1-D %s tensor of at least %d entries, got %s %s"
+                                 % (who, name, dtype, shape[1], getattr(t, "dtype", type(t).__name__),
+                                    tuple(getattr(t, "shape", ()))))
+            used.append(t)
+        else:
+            used.append(vec(t, name, dtype, shape))
+    for t in used:
+        _dev(t, "%s operand" % who)
+        if t.device != emissions.device:
+            raise ValueError("%s: operands on %s and %s" % (who, emissions.device, t.device))
+    return B, S, Cn
+
+
+def crf_constrained_llh(emissions, mask, allowed, start, end, trans, llh, log_z, log_za, infeasible=None):
+    """``llh = log Z_A - log Z`` of the paths inside the per-position allowed sets (``allowed`` int64 [B,S] bit sets), with
+    ``log_za`` and ``log_z`` (icka_crf_constrained_llh, include/icka_hip.h).  ``infeasible`` (int32 [1] or None) is ADDED to:
+    zero it first.  One launch, no host sync."""
+    who = "crf_constrained_llh"
+    B, S, Cn = _crf_constrained_check(who, emissions, mask, allowed, start, end, trans,
+                                      [(llh, "llh", F32, lambda B, S, C: (B,)), (log_z, "log_z", F32, lambda B, S, C: (B,)),
+                                       (log_za, "log_za", F32, lambda B, S, C: (B,)),
+                                       (infeasible, "infeasible", torch.int32, (1,))])
+    if llh is None or log_z is None or log_za is None:
+        raise ValueError("%s: llh, log_z and log_za are all written" % who)
+    check(_lib.load().icka_crf_constrained_llh(emissions.data_ptr(), Cn, _ptr(mask), allowed.data_ptr(), start.data_ptr(),
+                                               end.data_ptr(), trans.data_ptr(), llh.data_ptr(), log_z.data_ptr(),
+                                               log_za.data_ptr(), _ptr(infeasible), B, S, Cn, _stream()),
+          "icka_crf_constrained_llh")
+    return llh
+
+
+def crf_constrained_grad(emissions, mask, allowed, start, end, trans, gllh, d_emissions, d_start, d_end, d_trans):
+    """``gllh[b] * d llh[b] / d(.)`` of ``crf_constrained_llh``: ``d_emissions`` [B,S,C] is written, ``d_start``, ``d_end`` and
+    ``d_trans`` are ADDED to with atomics (the contract of ``crf_grad``).  One launch, no host sync."""
+    who = "crf_constrained_grad"
+    bsc = lambda B, S, C: (B, S, C)
+    B, S, Cn = _crf_constrained_check(who, emissions, mask, allowed, start, end, trans,
+                                      [(gllh, "gllh", F32, lambda B, S, C: (B,)), (d_emissions, "d_emissions", F32, bsc),
+                                       (d_start, "d_start", F32, lambda B, S, C: (C,)),
+                                       (d_end, "d_end", F32, lambda B, S, C: (C,)),
+                                       (d_trans, "d_trans", F32, lambda B, S, C: (C, C))])
+    if any(t is None for t in (gllh, d_emissions, d_start, d_end, d_trans)):
+        raise ValueError("%s: gllh and the four gradients are all needed" % who)
+    check(_lib.load().icka_crf_constrained_grad(emissions.data_ptr(), Cn, _ptr(mask), allowed.data_ptr(), start.data_ptr(),
+                                                end.data_ptr(), trans.data_ptr(), gllh.data_ptr(), d_emissions.data_ptr(), Cn,
+                                                d_start.data_ptr(), d_end.data_ptr(), d_trans.data_ptr(), B, S, Cn, _stream()),
+          "icka_crf_constrained_grad")
+
+
+def crf_constrained_decode(emissions, mask, allowed, start, end, trans, lens, tags_flat, scores, infeasible=None):
+    """The best path inside the allowed sets of every sample (icka_crf_constrained_decode, include/icka_hip.h): ``lens`` int32
+    [B], ``tags_flat`` int32 [>= B*S] in the layout of ``crf_score_decode``, ``scores`` f32 [B]; an infeasible sample holds -1
+    tags and a -inf score and adds 1 to ``infeasible`` (int32 [1] or None; zero it first).  One launch, no host sync."""
+    who = "crf_constrained_decode"
+    B, S, Cn = _crf_constrained_check(who, emissions, mask, allowed, start, end, trans,
+                                      [(lens, "lens", torch.int32, lambda B, S, C: (B,)),
+                                       (tags_flat, "tags_flat", torch.int32, lambda B, S, C: ("at least", B * S)),
+                                       (scores, "scores", F32, lambda B, S, C: (B,)),
+                                       (infeasible, "infeasible", torch.int32, (1,))], flat_b=True)
+    if lens is None or scores is None or tags_flat is None:
+        raise ValueError("%s: lens, tags_flat and scores are all written" % who)
+    check(_lib.load().icka_crf_constrained_decode(emissions.data_ptr(), Cn, _ptr(mask), allowed.data_ptr(), start.data_ptr(),
+                                                  end.data_ptr(), trans.data_ptr(), lens.data_ptr(), tags_flat.data_ptr(),
+                                                  tags_flat.numel(), scores.data_ptr(), _ptr(infeasible), B, S, Cn,
+                                                  _stream()),
+          "icka_crf_constrained_decode")
+
+
 # ------------------------------------------------------------------------------------------------- chunk metrics
 CHUNK_EVAL_MAX_S, CHUNK_EVAL_MAX_IDS, CHUNK_EVAL_MAX_TYPES, CHUNK_EVAL_HEAD = 512, 64, 32, 6
 

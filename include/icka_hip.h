@@ -636,6 +636,52 @@ int icka_crf_posterior(const float* emissions, int64_t ld, const int64_t* mask, 
 int icka_crf_nbest(const float* emissions, int64_t ld, const int64_t* mask, const float* start, const float* end,
                    const float* trans, int32_t nbest, int32_t* lens, int32_t* n_paths, float* scores, int32_t* tags_flat,
                    int64_t capacity, int32_t B, int32_t S, int32_t C, void* stream);
+/* The constrained CRF (csrc/crf_constrained.hip): every on-position carries a SET of allowed tags.  Training on partially
+ * labelled data maximises the marginal likelihood of all paths inside the sets; decoding returns the best path inside them.
+ * One launch per entry, one wave per sample, no host sync.  The chain is icka_crf_posterior's: per sample the ON-POSITIONS
+ * are position 0 and every t >= 1 with mask[b,t] != 0 (mask NULL = all on), L their number, x_0 .. x_{L-1} the emission rows
+ * at them, and
+ *   score(y) = start[y_0] + x_0[y_0] + sum_{i >= 1} (trans[y_{i-1}, y_i] + x_i[y_i]) + end[y_{L-1}].
+ * allowed int64 [B,S] in the layout of the mask: each entry is a bit set, bit j set = tag j allowed at that position.  Only
+ * on-positions are read; bits at or above C are ignored; C = 64 uses the sign bit, -1 means "every tag".  A_i is the set at
+ * on-position i,
+ *   Z_A = sum_{y : y_i in A_i for all i} exp score(y),   Z = sum_y exp score(y).
+ * icka_crf_constrained_llh:   llh[b] = log Z_A - log Z (<= 0), log_za[b] = log Z_A, log_z[b] = log Z, all f32 [B].
+ * icka_crf_constrained_grad:  gllh[b] * d llh[b] / d(.) with
+ *   d llh / d x_i[j] = mu^A_i(j) - mu_i(j), the difference of the restricted and the free token marginals; for start the
+ *   difference at i = 0, for end at i = L-1, for trans[u,v] the difference of the pair marginals summed over i >= 1.
+ *   d_emissions [B,S,C] (row stride ldd) is WRITTEN: every row of the sample, exact +0.0 in all C columns of an off-position
+ *   (the ldd - C pad columns are not touched).  d_start, d_end, d_trans are ACCUMULATED (+=) with atomics over the samples,
+ *   the contract of icka_crf_grad.
+ * INFEASIBLE samples: some on-position has no allowed tag below C (Z_A = 0).  llh and log_za are -inf, log_z is still
+ *   written; all d_emissions rows are exact zeros and the sample adds nothing to the parameter gradients; the llh and the
+ *   decode entry add 1 to infeasible (int32 [1], nullable; the caller zeroes it).  The other samples are unaffected and no
+ *   NaN appears anywhere: the restricted recursions do not run on such a sample.
+ * icka_crf_constrained_decode: argmax_{y in A} score(y) in the flat layout of icka_crf_score_decode: lens int32 [B] with
+ *   lens[b] = L, tags_flat int32 [capacity >= B*S] with sample b at sum(lens[0 .. b-1]) (summed inside the kernel; entries
+ *   past sum(lens) are left as they are), and scores f32 [B], summed in f32 from left to right as in icka_crf_nbest:
+ *   ((start + x_0) + trans) + x_1 .. + end.  TIE RULE: the first maximum over the allowed tags at both places (the previous
+ *   tag of every step and the final tag); with every tag allowed the path is icka_crf_score_decode's whenever mask[b,0] != 0
+ *   or mask is NULL.  An infeasible sample writes -1 into its L slots, gets scores[b] = -inf and is counted in infeasible.
+ * Emissions and parameters are assumed finite.  On non-finite input every stored tag is still in [0, C) or -1 and nothing
+ * outside the sample's own segment is touched.
+ * Limits (else ICKA_E_SHAPE, nothing launched): C <= 64, S*C <= 12288; for the decode entry B <= 2048.  Log-domain f32
+ * recursions, the free and the restricted lattice one after the other in the same wave: for C <= 16 with the scores on the
+ * lanes and the transitions in registers, otherwise through LDS (the same arithmetic in another summation order: neither
+ * form has a range the other lacks, so there is no fallback between them).
+ * Not covered: posteriors, N-best and entity confidences under constraints; transition-level constraints (write -1e4 into
+ * trans); packed batches. */
+int icka_crf_constrained_llh(const float* emissions, int64_t ld, const int64_t* mask, const int64_t* allowed,
+                             const float* start, const float* end, const float* trans, float* llh, float* log_z,
+                             float* log_za, int32_t* infeasible, int32_t B, int32_t S, int32_t C, void* stream);
+int icka_crf_constrained_grad(const float* emissions, int64_t ld, const int64_t* mask, const int64_t* allowed,
+                              const float* start, const float* end, const float* trans, const float* gllh,
+                              float* d_emissions, int64_t ldd, float* d_start, float* d_end, float* d_trans, int32_t B,
+                              int32_t S, int32_t C, void* stream);
+int icka_crf_constrained_decode(const float* emissions, int64_t ld, const int64_t* mask, const int64_t* allowed,
+                                const float* start, const float* end, const float* trans, int32_t* lens, int32_t* tags_flat,
+                                int64_t capacity, float* scores, int32_t* infeasible, int32_t B, int32_t S, int32_t C,
+                                void* stream);
 /* ---------------------------------------------------------------------------------------------------------------
  * Chunk-level scoring of a dev / test batch (csrc/metrics.hip): the counts behind the reference's accuracy / precision /
  * recall / F1, overall and per entity type -- the per-token loop of My_cross_attention.py:882-903 followed by
