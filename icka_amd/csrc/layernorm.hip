@@ -831,6 +831,10 @@ static int embed_bwd_impl(const void* dy, const int64_t* ids, const int64_t* tok
     EmbBwdArgs a{(const bf16_t*)dy, ids, token_type, (const bf16_t*)xhat, rstd, gamma, dword, dpos, dtype, partials,
                  B * S, S, H, vocab, n_type, padding_idx, make_drop(p_drop, seed), nullptr, nullptr, S, 0, 0, dtok};
     hipStream_t st = (hipStream_t)stream;
+    // more than two token types: dtype takes atomics (no slab slot, no finalize), so a fresh gradient starts from zero here
+    if (n_type > 2 && !accumulate &&
+        hipMemsetAsync(dtype, 0, sizeof(float) * (size_t)n_type * H, st) != hipSuccess)
+        return ICKA_E_ARG;
     int grid = bwd_grid(B * S);
     if (S <= BWD_BLOCKS) {   // position-major: one block per position, S slabs
         grid = S;

@@ -266,7 +266,11 @@ int icka_embed_fwd_h(const int64_t* ids, const int64_t* token_type, const float*
                      float p_drop, uint64_t seed, void* stream);
 /* Backward.  dword / dpos are ALWAYS accumulated into with f32 atomics (the caller zeroes them for a fresh
  * gradient); dtype / dgamma / dbeta follow `accumulate` as in icka_ln_bwd.  Row `padding_idx` of the word table
- * receives no gradient (nn.Embedding(padding_idx=0), :387).  partials: icka_ln_bwd_workspace_floats(H) floats. */
+ * receives no gradient (nn.Embedding(padding_idx=0), :387).  partials: icka_ln_bwd_workspace_floats(H) floats.
+ * With accumulate = 0, dtype starts from zero for every n_type (n_type > 2 takes atomics onto a cleared table).
+ * Ids and token types outside their table are CLAMPED, as in the forward: an id < 0 counts as row 0, an id >= vocab as
+ * row vocab - 1, and padding_idx is compared with the clamped id (id -3 with padding_idx = 0 is a padding token; with
+ * padding_idx = -1 no row is skipped).  dpos rows [0, S) are touched, no others.  H <= 2048 (64 KiB of dynamic LDS). */
 int icka_embed_bwd(const void* dy, const int64_t* ids, const int64_t* token_type, const void* xhat,
                    const float* rstd, const float* gamma, float* dword, float* dpos, float* dtype, float* dgamma,
                    float* dbeta, float* partials, int32_t B, int32_t S, int32_t H, int32_t vocab, int32_t n_type,
@@ -275,7 +279,10 @@ int icka_embed_bwd(const void* dy, const int64_t* ids, const int64_t* token_type
  * True); reference: apex DDP all-reduces the dense [vocab, H] gradient, My_cross_attention.py:768-776): as icka_embed_bwd, but
  * the word-table gradient is left as per-token rows dtok f32 [B*S, H] (zero rows for padding_idx).  After an all-gather of every
  * rank's rows and ids, icka_embed_scatter_rows adds scale * rows[t] into dword[ids[t]] (f32 atomics; rows f32 or bf16; the
- * padding id and ids outside [0, vocab) are skipped; the caller zeroes dword for a fresh gradient). */
+ * padding id and ids outside [0, vocab) are skipped; the caller zeroes dword for a fresh gradient).
+ * icka_embed_bwd_rows clamps ids as icka_embed_bwd does: dtok of a token whose CLAMPED id equals padding_idx is a zero row,
+ * every other row -- that of an id outside [0, vocab) included -- holds its gradient.  icka_embed_scatter_rows compares the
+ * ids AS GIVEN and skips those outside the table, so the two calls add up to icka_embed_bwd for ids inside [0, vocab) only. */
 int icka_embed_bwd_rows(const void* dy, const int64_t* ids, const int64_t* token_type, const void* xhat, const float* rstd,
                         const float* gamma, float* dtok, float* dpos, float* dtype, float* dgamma, float* dbeta, float* partials,
                         int32_t B, int32_t S, int32_t H, int32_t vocab, int32_t n_type, int32_t padding_idx, float p_drop,
@@ -296,7 +303,8 @@ int icka_embed_prompt_fwd(const int64_t* ids, const int32_t* src, const void* pr
                           int32_t H, int32_t vocab, int32_t pos_offset, float eps, float p_drop, uint64_t seed,
                           void* stream);
 /* Backward: table gradients as icka_embed_bwd (dtype = row 0 only), plus dprompt bf16 [B, P, H] (each row written
- * once).  S <= 1024.  partials: S * icka_ln_slab_slots() * H floats. */
+ * once: src must name every prompt vector exactly once).  dpos rows [pos_offset, pos_offset + S) are added into, no
+ * others.  S <= 1024 (ICKA_E_SHAPE beyond).  partials: S * icka_ln_slab_slots() * H floats. */
 int icka_embed_prompt_bwd(const void* dy, const int64_t* ids, const int32_t* src, const void* xhat, const float* rstd,
                           const float* gamma, float* dword, float* dpos, float* dtype, float* dgamma, float* dbeta,
                           void* dprompt, float* partials, int32_t B, int32_t S_in, int32_t S, int32_t P, int32_t H,

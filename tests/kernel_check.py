@@ -65,6 +65,18 @@ is the eps_fmt |ref| term of the bound; f32 outputs show how much room the accum
                     0.083, bias part < 0.001 (entries c >= C exactly zero); the slabs summed: dW 0.026, db 0.006
       contrastive   stats 0.226, ws 0.140, dt 0.024, dv 0.025, dcrs 0.265 (f32, bf16 and fp16 rows alike)
       (the device's __expf sigmoid meets the 2^-12, its expf / log1pf / expm1f the 2^-22 the bounds require of them.)
+    embedding family and flat buffers (tests/embed_check.py), worst over the cases of each kernel
+      embed         y 0.994, twin 0.993 (fp16; f32 below 0.1), xhat 0.993, rstd 0.060; backward dword 0.052, dtok 0.120,
+                    dpos 0.100, dtype 0.043, dgamma 0.235, dbeta 0.281 (both backward kernels, n_type 1 .. 3, H 8 .. 2048;
+                    untouched table rows and the padding row bitwise, dtok rows of the padding id exact zeros)
+      embed_prompt  y 0.992, twin 0.078, xhat 0.972, rstd 0.043; dprompt 0.990 (bf16), dword 0.037, dpos 0.024, dtype 0.008,
+                    dgamma 0.077, dbeta 0.023
+      embed_scatter_rows  dword 0.087 (f32 and bf16 rows, T up to 4 x 4096 + 3)
+      optim         sqnorm partials 0.004, norm 0.922 (f32 of a float64 sum: the bound IS the half ulp), coef < 0.001,
+                    adamw p 0.254, m 0.303, v 0.278 (u = 2^-24 per operation); shadows bitwise from the stored p,
+                    adamw_dev bitwise adamw
+      dp casts      cast_chunks and cast_back_scaled bitwise (a NaN becomes 0x7fc0); copy_many, zero_f32 bitwise;
+                    scalar_ratio 0.080, loss_accumulate exact
 
 No guard band was disturbed and no NaN pad reached a result in any case.  Two terms of the bounds go beyond the plain
 roundoff sums, both named in the docstrings below: the GELU allowance is RELATIVE (1e-4 |gelu|) for z >= 1, as
@@ -407,7 +419,7 @@ def ln_bwd_bounds(dy, xhat, rstd, gamma, mask=None):
     e_c2 = (H + 4) * U_ACC * (gd * xh).abs().mean(-1, keepdim=True)
     ds = r * (gd - c1 - xh * c2)
     e_ds = r * (2 * U_ACC * gd.abs() + e_c1 + xh.abs() * e_c2) + 3 * U_ACC * r * (gd.abs() + c1.abs() + (xh * c2).abs())
-    out = {"dres": (ds, stored(e_ds, ds, BF16))}
+    out = {"dres": (ds, stored(e_ds, ds, BF16)), "ds_raw": (ds, e_ds)}     # ds_raw: before any storage rounding
     m = torch.ones_like(ds) if mask is None else mask.double()
     dx = ds * m
     out["dx"] = (dx, stored(m * e_ds + U_ACC * dx.abs(), dx, BF16))
