@@ -103,6 +103,21 @@ class DeviceTags(object):
         return "DeviceTags(batch=%d, capacity=%d, device=%s)" % (self.batch_size, self.capacity, self.lens.device)
 
 
+def _check_reduction(reduction: str) -> None:
+    if reduction not in ("none", "sum", "mean", "token_mean"):
+        raise ValueError("invalid reduction: %s" % reduction)
+
+
+def _grads_for_atomics(mod, A: ParamArena):
+    """The three transition parameters of ``mod`` and their arena gradients, which the gradient kernels ADD to with atomics: so
+    they are zeroed here on the first write of an accumulation cycle."""
+    ps = (mod.start_transitions, mod.end_transitions, mod.transitions)
+    if A.grad_beta(ps) == 0.0:
+        for p in ps:
+            A.g(p).zero_()
+    return ps, tuple(A.g(p) for p in ps)
+
+
 class _CrfFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, emissions, tags, mask, mod, A: ParamArena):
@@ -116,16 +131,10 @@ class _CrfFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gllh):
         emissions, tags, mask = ctx.saved_tensors
-        mod, A = ctx.mod, ctx.A
-        ps = (mod.start_transitions, mod.end_transitions, mod.transitions)
-        if A.grad_beta(ps) == 0.0:          # first write of this accumulation cycle: the kernel adds with atomics
-            for p in ps:
-                A.g(p).zero_()
+        ps, gs = _grads_for_atomics(ctx.mod, ctx.A)
         de = torch.empty_like(emissions)
-        K.crf_grad(emissions, tags, mask, mod.start_transitions, mod.end_transitions, mod.transitions,
-                   gllh.to(F32).contiguous(), de, A.g(mod.start_transitions), A.g(mod.end_transitions),
-                   A.g(mod.transitions))
-        A.flush_final()
+        K.crf_grad(emissions, tags, mask, *ps, gllh.to(F32).contiguous(), de, *gs)
+        ctx.A.flush_final()
         return None, de, None, None, None, None
 
 
@@ -145,16 +154,10 @@ class _CrfConstrainedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gllh):
         emissions, allowed, mask = ctx.saved_tensors
-        mod, A = ctx.mod, ctx.A
-        ps = (mod.start_transitions, mod.end_transitions, mod.transitions)
-        if A.grad_beta(ps) == 0.0:          # first write of this accumulation cycle: the kernel adds with atomics
-            for p in ps:
-                A.g(p).zero_()
+        ps, gs = _grads_for_atomics(ctx.mod, ctx.A)
         de = torch.empty_like(emissions)
-        K.crf_constrained_grad(emissions, mask, allowed, mod.start_transitions, mod.end_transitions, mod.transitions,
-                               gllh.to(F32).contiguous(), de, A.g(mod.start_transitions), A.g(mod.end_transitions),
-                               A.g(mod.transitions))
-        A.flush_final()
+        K.crf_constrained_grad(emissions, mask, allowed, *ps, gllh.to(F32).contiguous(), de, *gs)
+        ctx.A.flush_final()
         return None, de, None, None, None, None
 
 
@@ -210,8 +213,7 @@ class CRF(ArenaModule):
         """Log-likelihood of ``tags`` given ``emissions`` (``none`` | ``sum`` | ``mean`` | ``token_mean``).
         Like the package, the first position of every sequence is treated as unmasked (the package raises when it is
         not; checking would cost a device->host sync, so it is not checked here)."""
-        if reduction not in ("none", "sum", "mean", "token_mean"):
-            raise ValueError("invalid reduction: %s" % reduction)
+        _check_reduction(reduction)
         e, t, m = self._prep(emissions, tags, mask)
         A = self._arena()
         llh = _CrfFn.apply(A.anchor, e, t, m, self, A)
@@ -244,8 +246,7 @@ class CRF(ArenaModule):
         """``(self.decode(emissions, mask), self(emissions, tags, mask, reduction))`` -- the dev pass of the reference.  Under
         ``device_decode()`` (and without autograd to feed) both come from ONE launch: ``(DeviceTags, llh)``, the llh bit for
         bit the forward's."""
-        if reduction not in ("none", "sum", "mean", "token_mean"):
-            raise ValueError("invalid reduction: %s" % reduction)
+        _check_reduction(reduction)
         if not device_decode_active() or (torch.is_grad_enabled() and
                                           (emissions.requires_grad or self.transitions.requires_grad)):
             return self.decode(emissions, mask), self(emissions, tags, mask, reduction)
@@ -447,8 +448,7 @@ class CRF(ArenaModule):
         are zeros.  No host sync.  The definitions are written out in include/icka_hip.h.  Posteriors, N-best and entity
         confidences under constraints, transition-level constraint arguments (write -1e4 into ``transitions``) and packed
         batches are not covered."""
-        if reduction not in ("none", "sum", "mean", "token_mean"):
-            raise ValueError("invalid reduction: %s" % reduction)
+        _check_reduction(reduction)
         e, m, al = self._prep_allowed("CRF.constrained_llh", emissions, allowed, mask)
         A = self._arena()
         llh = _CrfConstrainedFn.apply(A.anchor, e, al, m, self, A)
@@ -473,7 +473,28 @@ class CRF(ArenaModule):
         return out
 
 
-class ConstrainedPaths(object):
+class _JointBuffer(object):
+    """Named fields back to back in ONE int32 buffer, so that a result object reaches the host in one copy.  ``sizes``:
+    ``[(name, n_words)]`` in buffer order; ``slices[name]`` is a field's (first, past-the-last) word, ``joint`` the buffer."""
+
+    def __init__(self, sizes, device):
+        self.slices, o = {}, 0
+        for name, n in sizes:
+            self.slices[name] = (o, o + n)
+            o += n
+        self.joint = torch.empty(o, dtype=torch.int32, device=device)
+
+    def part(self, name: str, h: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The words of field ``name`` as a view of ``joint`` or, given one, of a host copy ``h`` of it."""
+        a, b = self.slices[name]
+        return (self.joint if h is None else h)[a:b]
+
+    def host(self) -> dict:
+        """``unpack`` of the one device-to-host copy of ``joint`` (a host sync)."""
+        return self.unpack(self.joint.cpu())
+
+
+class ConstrainedPaths(_JointBuffer):
     """The outputs of ``CRF.constrained_decode`` on the device, in ONE buffer (``joint``, int32 words; ``scores`` is an f32
     view of it) so that ``host()`` is one device-to-host copy:
 
@@ -484,30 +505,20 @@ class ConstrainedPaths(object):
 
     def __init__(self, B: int, S: int, device):
         cap = B * S
-        sizes = [("infeasible", 1), ("lens", B), ("tags_flat", cap), ("scores", B)]
-        self.slices, o = {}, 0
-        for name, n in sizes:
-            self.slices[name] = (o, o + n)
-            o += n
-        self.joint = torch.empty(o, dtype=torch.int32, device=device)
-        part = lambda name: self.joint[self.slices[name][0]:self.slices[name][1]]
+        super().__init__([("infeasible", 1), ("lens", B), ("tags_flat", cap), ("scores", B)], device)
+        part = self.part
         self.batch_size, self.capacity = B, cap
         self.infeasible = part("infeasible")
         self.tags = DeviceTags(part("lens"), part("tags_flat"))
         self.scores = part("scores").view(F32)
 
     def unpack(self, h: torch.Tensor) -> dict:
-        """``host()`` of a host copy ``h`` of ``joint`` the caller made (as part of a larger copy)."""
-        part = lambda name: h[self.slices[name][0]:self.slices[name][1]]
-        lens, flat = part("lens").tolist(), part("tags_flat").tolist()
+        """What ``host()`` returns, from a host copy ``h`` of ``joint`` (the caller's own, as part of a larger copy):
+        ``infeasible``, ``lens``, ``scores`` and ``paths`` (per sample a list of tags, None for an infeasible sample)."""
+        lens, flat = self.part("lens", h).tolist(), self.part("tags_flat", h).tolist()
         paths = [None if (p and p[0] < 0) else p for p in split_tags(lens, flat)]
-        return {"infeasible": int(part("infeasible")[0]), "lens": lens, "scores": part("scores").view(F32).tolist(),
-                "paths": paths}
-
-    def host(self) -> dict:
-        """``infeasible``, ``lens``, ``scores`` and ``paths`` (per sample a list of tags, None for an infeasible sample) on the
-        host: the one device-to-host copy (a host sync)."""
-        return self.unpack(self.joint.cpu())
+        return {"infeasible": int(self.part("infeasible", h)[0]), "lens": lens,
+                "scores": self.part("scores", h).view(F32).tolist(), "paths": paths}
 
     def tolist(self) -> List[Optional[List[int]]]:
         """Per sample its path, or None for an infeasible sample (one device-to-host copy)."""
@@ -517,7 +528,7 @@ class ConstrainedPaths(object):
         return "ConstrainedPaths(batch=%d, capacity=%d, device=%s)" % (self.batch_size, self.capacity, self.joint.device)
 
 
-class CrfPosterior(object):
+class CrfPosterior(_JointBuffer):
     """The outputs of ``CRF.posterior`` on the device, all but the marginals in ONE buffer (``joint``, int32 words; the f32
     fields are views of it) so that ``host()`` is one device-to-host copy:
 
@@ -530,14 +541,10 @@ class CrfPosterior(object):
 
     def __init__(self, B: int, S: int, device, entities: bool):
         cap = B * S
-        sizes = [("bad", 1), ("lens", B), ("tags_flat", cap), ("n_ent", B if entities else 0), ("ent", 3 * cap if entities else 0),
-                 ("log_z", B), ("seq_logp", B), ("token_conf", cap), ("ent_conf", cap if entities else 0)]
-        self.slices, o = {}, 0
-        for name, n in sizes:
-            self.slices[name] = (o, o + n)
-            o += n
-        self.joint = torch.empty(o, dtype=torch.int32, device=device)
-        part = lambda name: self.joint[self.slices[name][0]:self.slices[name][1]]
+        super().__init__([("bad", 1), ("lens", B), ("tags_flat", cap), ("n_ent", B if entities else 0),
+                          ("ent", 3 * cap if entities else 0), ("log_z", B), ("seq_logp", B), ("token_conf", cap),
+                          ("ent_conf", cap if entities else 0)], device)
+        part = self.part
         self.batch_size, self.capacity = B, cap
         self.bad = part("bad")
         self.tags = DeviceTags(part("lens"), part("tags_flat"))
@@ -558,8 +565,9 @@ class CrfPosterior(object):
     def unpack(self, h: torch.Tensor) -> dict:
         """``host()`` of a host copy ``h`` of ``joint`` the caller made (as part of a larger copy)."""
         out = {}
-        for name, (a, b) in self.slices.items():
-            out[name] = (h[a:b].view(F32) if name in ("log_z", "seq_logp", "token_conf", "ent_conf") else h[a:b]).tolist()
+        for name in self.slices:
+            w = self.part(name, h)
+            out[name] = (w.view(F32) if name in ("log_z", "seq_logp", "token_conf", "ent_conf") else w).tolist()
         out["bad"] = out["bad"][0]
         return out
 
@@ -568,7 +576,7 @@ class CrfPosterior(object):
             self.batch_size, self.capacity, self.ent is not None, self.joint.device)
 
 
-class NBestPaths(object):
+class NBestPaths(_JointBuffer):
     """The outputs of ``CRF.decode_nbest`` on the device, in ONE buffer (``joint``, int32 words; ``scores`` is an f32 view of
     it) so that ``host()`` is one device-to-host copy:
 
@@ -581,13 +589,8 @@ class NBestPaths(object):
 
     def __init__(self, B: int, S: int, nbest: int, device):
         cap = B * S
-        sizes = [("lens", B), ("n_paths", B), ("scores", B * nbest), ("tags", nbest * cap)]
-        self.slices, o = {}, 0
-        for name, n in sizes:
-            self.slices[name] = (o, o + n)
-            o += n
-        self.joint = torch.empty(o, dtype=torch.int32, device=device)
-        part = lambda name: self.joint[self.slices[name][0]:self.slices[name][1]]
+        super().__init__([("lens", B), ("n_paths", B), ("scores", B * nbest), ("tags", nbest * cap)], device)
+        part = self.part
         self.batch_size, self.capacity, self.nbest = B, cap, nbest
         self.lens, self.n_paths = part("lens"), part("n_paths")
         self.scores = part("scores").view(F32).view(B, nbest)
@@ -609,16 +612,11 @@ class NBestPaths(object):
         return self.scores - log_z.to(F32)[:, None]
 
     def unpack(self, h: torch.Tensor) -> dict:
-        """``host()`` of a host copy ``h`` of ``joint`` the caller made (as part of a larger copy)."""
-        part = lambda name: h[self.slices[name][0]:self.slices[name][1]]
-        return {"lens": part("lens").tolist(), "n_paths": part("n_paths").tolist(),
-                "scores": part("scores").view(F32).view(self.batch_size, self.nbest).tolist(),
-                "tags": part("tags").view(self.nbest, self.capacity).tolist()}
-
-    def host(self) -> dict:
-        """Everything on the host as python lists keyed by field name (``scores`` and ``tags`` nested by row): the one
-        device-to-host copy (a host sync)."""
-        return self.unpack(self.joint.cpu())
+        """What ``host()`` returns, from a host copy ``h`` of ``joint`` (the caller's own, as part of a larger copy):
+        python lists keyed by field name, ``scores`` and ``tags`` nested by row."""
+        return {"lens": self.part("lens", h).tolist(), "n_paths": self.part("n_paths", h).tolist(),
+                "scores": self.part("scores", h).view(F32).view(self.batch_size, self.nbest).tolist(),
+                "tags": self.part("tags", h).view(self.nbest, self.capacity).tolist()}
 
     @staticmethod
     def paths_of(h: dict) -> List[List[tuple]]:

@@ -11,11 +11,9 @@
 //   and the end transition is taken at position sum(mask) - 1.
 #include <math.h>
 
-#include "common.h"
+#include "crf_core.h"
 
 namespace {
-
-constexpr int CRF_MAX_SC = 12288;   // S * C floats of per-position scores kept in LDS by the gradient kernel (48 KiB)
 
 struct CrfArgs {
     const float* e; int64_t ld_s;   // emissions [B, S, C]: element (b, t, j) at e[(b*S + t)*ld_s + j]
@@ -33,9 +31,6 @@ struct CrfArgs {
 __device__ __forceinline__ int tag_at(const int64_t* tg, int t, int C) {
     const int64_t y = tg[t];
     return y < 0 ? 0 : (y >= C ? C - 1 : (int)y);
-}
-__device__ __forceinline__ bool on(const CrfArgs& a, int b, int t) {
-    return t == 0 || a.mask == nullptr || a.mask[(int64_t)b * a.S + t] != 0;
 }
 
 // log-sum-exp (or max) over i of  s_alpha[i] + s_T[i*C + j]  for this lane's tag j
@@ -59,7 +54,7 @@ __device__ __forceinline__ float gold_score(const CrfArgs& a, int b, int lane) {
     float s = 0.f;
     int cnt = 0;
     for (int t = lane; t < a.S; t += 64) {
-        const bool act = on(a, b, t);
+        const bool act = on_pos(a, b, t);
         cnt += (a.mask == nullptr || a.mask[(int64_t)b * a.S + t] != 0) ? 1 : 0;
         if (!act) continue;
         const int y = tag_at(tg, t, a.C);
@@ -82,7 +77,7 @@ __device__ __forceinline__ void crf_llh_body(const CrfArgs& a, float* s_T, float
     const float* eb = a.e + (int64_t)b * a.S * a.ld_s;
     float alpha = j < C ? a.start[j] + eb[j] : -INFINITY;
     for (int t = 1; t < a.S; ++t) {
-        if (!on(a, b, t)) continue;   // wave-uniform
+        if (!on_pos(a, b, t)) continue;   // wave-uniform
         __syncthreads();   // block = one wave: orders the LDS exchange
         if (j < C) s_alpha[j] = alpha;
         __syncthreads();   // block = one wave: orders the LDS exchange
@@ -120,7 +115,7 @@ __global__ __launch_bounds__(64) void crf_grad_kernel(const CrfArgs a) {
     if (j < C) s_al[j] = alpha;
     int len = 1;
     for (int t = 1; t < S; ++t) {
-        const bool act = on(a, b, t);
+        const bool act = on_pos(a, b, t);
         len += (a.mask == nullptr || a.mask[(int64_t)b * S + t] != 0) ? 1 : 0;
         if (act) {
             __syncthreads();   // block = one wave: orders the LDS exchange
@@ -139,7 +134,7 @@ __global__ __launch_bounds__(64) void crf_grad_kernel(const CrfArgs a) {
     float dend = j < C ? -__expf(v - logz) : 0.f;   // - P(y_last = j)
     float dstart = 0.f;
     for (int t = S - 1; t >= 0; --t) {
-        const bool act = on(a, b, t);
+        const bool act = on_pos(a, b, t);
         if (!act) {
             if (j < C) deb[(int64_t)t * a.ld_ds + j] = 0.f;
             continue;
@@ -189,7 +184,7 @@ __device__ __forceinline__ int crf_viterbi_lds(const CrfArgs& a, float* s_T, flo
     float score = j < C ? a.start[j] + eb[j] : -INFINITY;
     int len = 1;
     for (int t = 1; t < S; ++t) {
-        const bool act = on(a, b, t);
+        const bool act = on_pos(a, b, t);
         len += (a.mask == nullptr || a.mask[(int64_t)b * S + t] != 0) ? 1 : 0;
         __syncthreads();   // block = one wave: orders the LDS exchange
         if (j < C) s_alpha[j] = score;
@@ -242,7 +237,7 @@ __global__ __launch_bounds__(64) void crf_decode_kernel(const CrfArgs a) {
     float score = j < C ? a.start[j] + eb[j] : -INFINITY;
     int len = 1;
     for (int t = 1; t < S; ++t) {
-        const bool act = on(a, b, t);
+        const bool act = on_pos(a, b, t);
         len += (a.mask == nullptr || a.mask[(int64_t)b * S + t] != 0) ? 1 : 0;
         __syncthreads();   // block = one wave: orders the LDS exchange
         if (j < C) s_alpha[j] = score;
@@ -279,12 +274,9 @@ __global__ __launch_bounds__(64) void crf_decode_kernel(const CrfArgs a) {
 // Register / shuffle variants for C <= 16 tags (the reference has 13 / 15 labels): the transition column (and row) of
 // a lane's tag live in registers, the running scores are exchanged with wave shuffles, the mask is a bit set built
 // with one ballot per 64 positions and the next step's emissions are prefetched -- no LDS traffic or barrier inside
-// the S-step recursions (the LDS versions above spend ~3.5k cycles per step on them).
-constexpr int CM = 16;
-constexpr int MAXW = 8;   // mask words: S <= 512
-
+// the S-step recursions (the LDS versions above spend ~3.5k cycles per step on them).  CM tags, CRF_WORDS mask words.
 struct MaskBits {
-    unsigned long long w[MAXW];
+    unsigned long long w[CRF_WORDS];
     __device__ __forceinline__ bool on(int t) const { return t == 0 || ((w[t >> 6] >> (t & 63)) & 1ull); }
     __device__ __forceinline__ bool raw(int t) const { return (w[t >> 6] >> (t & 63)) & 1ull; }
 };
@@ -292,7 +284,7 @@ __device__ __forceinline__ MaskBits load_mask(const CrfArgs& a, int b, int lane,
     MaskBits mb;
     int n = 0;
 #pragma unroll
-    for (int k = 0; k < MAXW; ++k) {
+    for (int k = 0; k < CRF_WORDS; ++k) {
         const int t = 64 * k + lane;
         const bool v = t < a.S && (a.mask == nullptr || a.mask[(int64_t)b * a.S + t] != 0);
         mb.w[k] = __ballot(v);
@@ -422,44 +414,8 @@ __device__ __noinline__ void crf_grad_small_log(const CrfArgs& a, const MaskBits
 // beside the chain.  Backward: bhat_{t-1}[i] = sum_j E[i][j] x_t[j] bhat_t[j] / c_t, marginal_t = a_t . bhat_t,
 // pair marginals a_{t-1}[i] E[i][j] x_t[j] bhat_t[j] / c_t.  If a normaliser underflows (spreads beyond ~e^80, e.g.
 // -1e4 "forbidden" transitions into every reachable tag) or a marginal is not finite the sample is redone by the
-// log-domain body above: same results either way up to f32 rounding.
-// 16-lane row reductions on the DPP path (row_ror: no LDS crossbar, ~4 VALU ops): every lane of the row gets the result
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sum16(float v) {
-    v += dpp_f<0x128>(v);   // row_ror:8
-    v += dpp_f<0x124>(v);   // row_ror:4
-    v += dpp_f<0x122>(v);   // row_ror:2
-    v += dpp_f<0x121>(v);   // row_ror:1
-    return v;
-}
-__device__ __forceinline__ float max16(float v) {
-    v = fmaxf(v, dpp_f<0x128>(v));
-    v = fmaxf(v, dpp_f<0x124>(v));
-    v = fmaxf(v, dpp_f<0x122>(v));
-    v = fmaxf(v, dpp_f<0x121>(v));
-    return v;
-}
-__device__ __forceinline__ float lane_val(float x, int i) {   // value of lane i (compile-time i) as a scalar operand
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), i));
-}
-// sum_i (value of lane i) * col[i]
-__device__ __forceinline__ float dot_shfl(float x, const float (&col)[CM]) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-    for (int i = 0; i < CM; i += 4) {
-        s0 = fmaf(lane_val(x, i), col[i], s0);
-        s1 = fmaf(lane_val(x, i + 1), col[i + 1], s1);
-        s2 = fmaf(lane_val(x, i + 2), col[i + 2], s2);
-        s3 = fmaf(lane_val(x, i + 3), col[i + 3], s3);
-    }
-    return (s0 + s1) + (s2 + s3);
-}
-constexpr float CRF_TINY = 1e-30f;
-constexpr int CRF_LIN_SC = 4096;   // S * C of the scaled form: x_t and a_t tiles of 16 KiB each
-
+// log-domain body above: same results either way up to f32 rounding.  (The 16-lane row sums, maxima and dot products are
+// crf_core.h's sum16 / max16 / dot_shfl.)
 struct CrfLin {
     float logz;      // log partition function
     float zend;      // sum_j a_last[j] exp(end[j] - mEnd)
@@ -563,7 +519,7 @@ __device__ __forceinline__ bool crf_llh_small_lin(const CrfArgs& a, float* s_x, 
 
 __global__ __launch_bounds__(64) void crf_llh_small_kernel(const CrfArgs a) {
     __shared__ float s_x[CRF_LIN_SC];
-    __shared__ unsigned char s_on[64 * MAXW];
+    __shared__ unsigned char s_on[CRF_WORDS_MAX_S];
     const int b = blockIdx.x, j = threadIdx.x;
     if (crf_llh_small_lin(a, s_x, s_on)) return;
     int len;
@@ -573,8 +529,8 @@ __global__ __launch_bounds__(64) void crf_llh_small_kernel(const CrfArgs a) {
 
 __global__ __launch_bounds__(64) void crf_grad_small_kernel(const CrfArgs a) {
     __shared__ float s_buf[CRF_MAX_SC];   // scaled form: a_t[j] | x_t[j] (S * C <= 4096 each); log form: alpha[t][j]
-    __shared__ float s_c[64 * MAXW];
-    __shared__ unsigned char s_tag[64 * MAXW], s_on[64 * MAXW];
+    __shared__ float s_c[CRF_WORDS_MAX_S];
+    __shared__ unsigned char s_tag[CRF_WORDS_MAX_S], s_on[CRF_WORDS_MAX_S];
     const int b = blockIdx.x, j = threadIdx.x, C = a.C, S = a.S;
     const bool act_lane = j < C;
     bool ok = S * C <= CRF_LIN_SC;
@@ -633,7 +589,7 @@ __global__ __launch_bounds__(64) void crf_grad_small_kernel(const CrfArgs a) {
                 // u[j] = x_t[j] bhat_t[j] / S_{t-1};  pair marginal (i, j) = a_{t-1}[i] E[i][j] u[j]
                 const float u = xc * bh;
 #pragma unroll
-                for (int i = 0; i < CM; ++i) dT[i] = fmaf(-lane_val(ap, i) * Ec[i], u, dT[i]);
+                for (int i = 0; i < CM; ++i) dT[i] = fmaf(-lane_f32(ap, i) * Ec[i], u, dT[i]);
                 if (j == y) {   // gold transition (literal previous position)
 #pragma unroll
                     for (int i = 0; i < CM; ++i) dT[i] += (i == yp) ? 1.f : 0.f;
@@ -701,7 +657,7 @@ __device__ __forceinline__ int crf_viterbi_small(const CrfArgs& a, unsigned char
         int am = 0;
 #pragma unroll
         for (int i = 0; i < CM; ++i) {
-            const float v = lane_val(score, i) + Tc[i];
+            const float v = lane_f32(score, i) + Tc[i];
             if (v > m) { m = v; am = i; }
         }
         if (act_lane) {
@@ -717,7 +673,7 @@ __device__ __forceinline__ int crf_viterbi_small(const CrfArgs& a, unsigned char
 __global__ __launch_bounds__(64) void crf_decode_small_kernel(const CrfArgs a) {
     __shared__ unsigned char s_bp[CRF_MAX_SC];
     __shared__ float s_e[CRF_LIN_SC];
-    __shared__ unsigned char s_on[64 * MAXW];
+    __shared__ unsigned char s_on[CRF_WORDS_MAX_S];
     __shared__ float s_fin[64];
     const int len = crf_viterbi_small(a, s_bp, s_e, s_on, s_fin);
     if (threadIdx.x == 0) crf_backtrace<true>(a, s_fin, s_bp, len, a.best, (int64_t)blockIdx.x * a.S, a.best_score);
@@ -728,8 +684,6 @@ __global__ __launch_bounds__(64) void crf_decode_small_kernel(const CrfArgs a) {
 // bodies, so the same bits), then the Viterbi path written WITHOUT padding into tags_flat at this sample's exclusive prefix
 // of the path lengths.  Each wave computes that prefix itself from the mask rows before its own (one ballot per 64
 // positions): no cross-block hand-off, B * b * S mask reads in all, a few microseconds at the B <= 2048 the entry accepts.
-constexpr int CRF_FLAT_MAX_B = 2048;
-
 struct CrfFlatArgs {
     CrfArgs a;
     int32_t* lens;   // [B]: path length of each sample
@@ -782,7 +736,7 @@ __global__ __launch_bounds__(64) void crf_score_decode_kernel(const CrfFlatArgs 
 __global__ __launch_bounds__(64) void crf_score_decode_small_kernel(const CrfFlatArgs d) {
     __shared__ unsigned char s_bp[CRF_MAX_SC];
     __shared__ float s_e[CRF_LIN_SC];   // the likelihood's x_t, then the decode's emissions
-    __shared__ unsigned char s_on[64 * MAXW];
+    __shared__ unsigned char s_on[CRF_WORDS_MAX_S];
     __shared__ float s_fin[64];
     const CrfArgs& a = d.a;
     if (a.tags && !crf_llh_small_lin(a, s_e, s_on)) {
@@ -797,7 +751,7 @@ __global__ __launch_bounds__(64) void crf_score_decode_small_kernel(const CrfFla
     crf_write_flat(d, s_fin, s_bp, len);
 }
 
-inline bool crf_small(int S, int C) { return C <= CM && S <= 64 * MAXW; }
+inline bool crf_small(int S, int C) { return C <= CM && S <= CRF_WORDS_MAX_S; }
 
 inline int crf_check(const void* e, const void* start, const void* end, const void* trans, int B, int S, int C) {
     if (!e || !start || !end || !trans) return ICKA_E_ARG;

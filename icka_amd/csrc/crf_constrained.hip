@@ -23,12 +23,10 @@
 //   crf_grad_kernel takes: two blocks per 160 KiB gfx950 CU; both lattices side by side would take 128 KiB).
 #include <math.h>
 
-#include "common.h"
+#include "crf_core.h"
 
 namespace {
 
-constexpr int CRF_MAX_SC = 12288;       // S * C per sample (as icka_crf_grad / icka_crf_score_decode)
-constexpr int CRF_FLAT_MAX_B = 2048;    // the wave sums the path lengths of the samples before its own itself
 constexpr int ON_WORDS = CRF_MAX_SC / 64;   // S <= 12288 (C = 1): 64 positions per word
 typedef unsigned long long u64;
 
@@ -42,9 +40,6 @@ struct ConArgs {
     int B, S, C;
 };
 
-__device__ __forceinline__ bool on_pos(const ConArgs& a, int b, int t) {
-    return t == 0 || a.mask == nullptr || a.mask[(int64_t)b * a.S + t] != 0;
-}
 __device__ __forceinline__ unsigned long long tag_bits(int C) { return C >= 64 ? ~0ull : (1ull << C) - 1ull; }
 __device__ __forceinline__ unsigned long long allowed_at(const ConArgs& a, int b, int t) {
     return (unsigned long long)a.allowed[(int64_t)b * a.S + t];
@@ -196,9 +191,7 @@ __device__ __forceinline__ void con_backward(const ConArgs& a, int b, int j, int
     }
 }
 
-// ------------------------------------------------------------------------------------------------ register form
-constexpr int CM = 16;   // tags of the register form
-
+// ------------------------------------------------------------------------------------------------ register form (C <= CM)
 // lse_k (value of lane k + col[k]) over the CM lanes of the tags; col[k] = -inf for k >= C
 __device__ __forceinline__ float lse_lanes(float x, const float (&col)[CM]) {
     float v[CM];

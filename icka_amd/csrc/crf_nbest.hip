@@ -19,16 +19,13 @@
 // paths are meaningless but no access leaves the sample's own segment.  All global stores are ordinary vector stores.
 #include <math.h>
 
-#include "common.h"
+#include "crf_core.h"
 
 namespace {
 
 constexpr int NB_MAX_C = 16;
 constexpr int NB_MAX_K = 8;
-constexpr int NB_MAX_S = 512;
-constexpr int NB_MAX_B = 2048;          // the wave sums the path lengths of the samples before its own (as icka_crf_score_decode)
 constexpr int NB_BP_BYTES = 49152;      // S * C * K
-constexpr int NB_PW = NB_MAX_S / 64;    // 64-position mask words
 
 struct NbestArgs {
     const float* e; int64_t ld;
@@ -37,8 +34,6 @@ struct NbestArgs {
     int32_t* lens; int32_t* n_paths; float* scores; int32_t* flat; int64_t cap;
     int B, S, C, K;
 };
-
-__device__ __forceinline__ unsigned long long nb_lanes_below(int lane) { return (1ull << lane) - 1ull; }
 
 template <int CTRL>
 __device__ __forceinline__ int nb_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
@@ -113,7 +108,7 @@ __device__ __forceinline__ void nb_merge(const float* prev, int K, int C, int cn
 __global__ __launch_bounds__(64) void crf_nbest_kernel(const NbestArgs a) {
     __shared__ unsigned char s_bp[NB_BP_BYTES];
     __shared__ float s_sc[2][NB_MAX_C * NB_MAX_K];
-    __shared__ unsigned short s_pos[NB_MAX_S];
+    __shared__ unsigned short s_pos[CRF_WORDS_MAX_S];
     __shared__ int s_fin[NB_MAX_K];
     const int b = blockIdx.x, lane = threadIdx.x, S = a.S, C = a.C, K = a.K;
     const int c = lane >> 2, q = lane & 3;
@@ -121,16 +116,16 @@ __global__ __launch_bounds__(64) void crf_nbest_kernel(const NbestArgs a) {
     // the on-positions, compacted in order (crf_posterior.hip)
     // (mask loads go out unconditionally at clamped indices, eight in flight, and are dropped by a select: a guarded load
     // compiles to a branch that waits for it)
-    int64_t mw[NB_PW];
+    int64_t mw[CRF_WORDS];
 #pragma unroll
-    for (int w = 0; w < NB_PW; ++w) mw[w] = a.mask ? a.mask[(int64_t)b * S + min(64 * w + lane, S - 1)] : 1;
+    for (int w = 0; w < CRF_WORDS; ++w) mw[w] = a.mask ? a.mask[(int64_t)b * S + min(64 * w + lane, S - 1)] : 1;
     int L = 0;
 #pragma unroll
-    for (int w = 0; w < NB_PW; ++w) {
+    for (int w = 0; w < CRF_WORDS; ++w) {
         const int t = 64 * w + lane;
         const bool on = t < S && (t == 0 || mw[w] != 0);
         const unsigned long long km = __ballot(on);
-        if (on) s_pos[L + __popcll(km & nb_lanes_below(lane))] = (unsigned short)t;
+        if (on) s_pos[L + __popcll(km & lanes_below(lane))] = (unsigned short)t;
         L += __popcll(km);
     }
     // sum of the path lengths of the samples before this one: b + the non-zero mask entries at their positions >= 1
@@ -138,11 +133,11 @@ __global__ __launch_bounds__(64) void crf_nbest_kernel(const NbestArgs a) {
     if (a.mask != nullptr) {
         const int n = b * S;   // <= 2^20
         int nz = 0;
-        for (int base = 0; base < n; base += 64 * NB_PW) {
+        for (int base = 0; base < n; base += 64 * CRF_WORDS) {
 #pragma unroll
-            for (int u = 0; u < NB_PW; ++u) mw[u] = a.mask[min(base + 64 * u + lane, n - 1)];
+            for (int u = 0; u < CRF_WORDS; ++u) mw[u] = a.mask[min(base + 64 * u + lane, n - 1)];
 #pragma unroll
-            for (int u = 0; u < NB_PW; ++u) nz += (base + 64 * u + lane < n && mw[u] != 0) ? 1 : 0;
+            for (int u = 0; u < CRF_WORDS; ++u) nz += (base + 64 * u + lane < n && mw[u] != 0) ? 1 : 0;
         }
         for (int r = lane; r < b; r += 64) nz -= a.mask[(int64_t)r * S] != 0 ? 1 : 0;   // position 0 counts whatever its mask says
 #pragma unroll
@@ -237,7 +232,7 @@ extern "C" int icka_crf_nbest(const float* emissions, int64_t ld, const int64_t*
                               int32_t* tags_flat, int64_t capacity, int32_t B, int32_t S, int32_t C, void* stream) {
     if (!emissions || !start || !end || !trans || !lens || !n_paths || !scores || !tags_flat || ld < C) return ICKA_E_ARG;
     if (B <= 0 || S <= 0 || C <= 0 || nbest <= 0) return ICKA_E_SHAPE;
-    if (C > NB_MAX_C || nbest > NB_MAX_K || S > NB_MAX_S || B > NB_MAX_B) return ICKA_E_SHAPE;
+    if (C > NB_MAX_C || nbest > NB_MAX_K || S > CRF_WORDS_MAX_S || B > CRF_FLAT_MAX_B) return ICKA_E_SHAPE;
     if ((int64_t)S * C * nbest > NB_BP_BYTES || capacity < (int64_t)B * S) return ICKA_E_SHAPE;
     NbestArgs a{};
     a.e = emissions; a.ld = ld; a.mask = mask; a.start = start; a.end = end; a.trans = trans;

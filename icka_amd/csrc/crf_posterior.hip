@@ -15,23 +15,15 @@
 // so the posterior of a span s .. e-1 is tc_s exp(R_{e-1} - R_s) with R the prefix sums of r: alpha_s psi .. psi beta_{e-1} / Z
 // with the inner betas telescoped away.  Every r_i is of the size of one step's log-probability, never of the size of the
 // accumulated scores, so the difference of two prefix sums keeps its digits on long spans.
-// Helpers equal to crf.hip's are COPIES: that file's kernels are left as they are (their register counts are sensitive).
+// The limits, the label-word bits, chunk_flags, on_pos and the 16-lane primitives (sum16 / max16 / dot_shfl) are crf_core.h's.
 #include <math.h>
 
-#include "common.h"
+#include "crf_core.h"
 
 namespace {
 
-constexpr int CRF_MAX_SC = 12288;       // S * C per sample (as icka_crf_grad / icka_crf_score_decode)
-constexpr int CRF_FLAT_MAX_B = 2048;    // the wave sums lens[r < b] itself (as icka_crf_score_decode)
-constexpr int CRF_LIN_SC = 4096;        // the scaled form's a_i and x_i tiles
-constexpr int CM = 16;                  // tags of the register / shuffle form
-constexpr int PW = 8;                   // 64-position words of the chunk pass: S <= 512
-constexpr int P_MAX_S = 64 * PW;
 constexpr int P_MAX_L = 64;             // label-table words
-constexpr float CRF_TINY = 1e-30f;
 constexpr float R_FLOOR = -128.f;       // log of a conditional probability that underflowed: exp(R_FLOOR) == 0 in f32
-constexpr uint32_t LT_DEFAULT = 1u, LT_BEGIN = 2u;   // label_table word bits (metrics.hip), type id from bit 8 up
 
 struct PostArgs {
     const float* e; int64_t ld;
@@ -52,44 +44,8 @@ struct PostLds {
     float* g;              // [<= 512] scaled step factor (scaled) / emission of the path tag (log); then r_i, then R_i
     uint32_t* w;           // [<= 512] label-table words of the path
     uint32_t* table;       // [64]
-    unsigned long long* term;   // [PW]
+    unsigned long long* term;   // [CRF_WORDS]
 };
-
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
-__device__ __forceinline__ bool on_pos(const PostArgs& a, int b, int t) {
-    return t == 0 || a.mask == nullptr || a.mask[(int64_t)b * a.S + t] != 0;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sum16(float v) {   // every lane of a 16-lane row gets the row's sum (row_ror 8, 4, 2, 1)
-    v += dpp_f<0x128>(v);
-    v += dpp_f<0x124>(v);
-    v += dpp_f<0x122>(v);
-    v += dpp_f<0x121>(v);
-    return v;
-}
-__device__ __forceinline__ float max16(float v) {
-    v = fmaxf(v, dpp_f<0x128>(v));
-    v = fmaxf(v, dpp_f<0x124>(v));
-    v = fmaxf(v, dpp_f<0x122>(v));
-    v = fmaxf(v, dpp_f<0x121>(v));
-    return v;
-}
-// sum_i (value of lane i) * col[i]
-__device__ __forceinline__ float dot_shfl(float x, const float (&col)[CM]) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-    for (int i = 0; i < CM; i += 4) {
-        s0 = fmaf(lane_f32(x, i), col[i], s0);
-        s1 = fmaf(lane_f32(x, i + 1), col[i + 1], s1);
-        s2 = fmaf(lane_f32(x, i + 2), col[i + 2], s2);
-        s3 = fmaf(lane_f32(x, i + 3), col[i + 3], s3);
-    }
-    return (s0 + s1) + (s2 + s3);
-}
 
 // ------------------------------------------------------------------------------------------------------ the path
 // Exclusive prefix of lens, the number of on-positions L, the checks of the contract, and the path tags into LDS.
@@ -150,20 +106,13 @@ __device__ __forceinline__ void post_zero_off(const PostArgs& a, int b, int lane
 }
 
 // ------------------------------------------------------------------------------------------------------ chunks
-// start / term of position i from its label word and the word before it (metrics.hip chunk_flags)
-__device__ __forceinline__ void chunk_flags(uint32_t w, uint32_t wp, bool first, bool in, bool& start, bool& term) {
-    const bool o = (w & LT_DEFAULT) != 0;
-    const bool po = (wp & LT_DEFAULT) != 0;
-    start = in && !o && (first || po || (w >> 8) != (wp >> 8) || (w & LT_BEGIN) != 0);
-    term = in && (o || start);
-}
-
+// (start / term of a position: chunk_flags, crf_core.h)
 // The chunks of the path and their posteriors.  In: p.y, p.tc, p.g = r_i (i >= 1), p.table.  L <= 512.
 __device__ __forceinline__ void post_chunks(const PostArgs& a, const PostLds& p, int b, int lane, long long off, int L) {
     // label words; prefix sums R of r (in place), one 64-lane scan per word with the carry of the words before
     float carry = 0.f;
 #pragma unroll
-    for (int k = 0; k < PW; ++k) {
+    for (int k = 0; k < CRF_WORDS; ++k) {
         const int i = 64 * k + lane;
         const bool in = i < L;
         if (in) {
@@ -181,11 +130,11 @@ __device__ __forceinline__ void post_chunks(const PostArgs& a, const PostLds& p,
         carry = __shfl(v, 63, 64);
     }
     __syncthreads();   // block = one wave: words and prefix sums are in LDS
-    int rank[PW];
+    int rank[CRF_WORDS];
     uint32_t starts = 0u;
     int n = 0;
 #pragma unroll
-    for (int k = 0; k < PW; ++k) {
+    for (int k = 0; k < CRF_WORDS; ++k) {
         const int i = 64 * k + lane;
         const bool in = i < L;
         const uint32_t w = in ? p.w[i] : 0u, wp = (in && i > 0) ? p.w[i - 1] : 0u;
@@ -199,13 +148,13 @@ __device__ __forceinline__ void post_chunks(const PostArgs& a, const PostLds& p,
     }
     __syncthreads();   // block = one wave: the term words are in LDS
 #pragma unroll
-    for (int k = 0; k < PW; ++k) {
+    for (int k = 0; k < CRF_WORDS; ++k) {
         if (!((starts >> k) & 1u)) continue;
         const int i = 64 * k + lane;
         int e = L;   // no term after i: the chunk runs to the end of the path
         bool found = false;
 #pragma unroll
-        for (int q = k; q < PW; ++q) {
+        for (int q = k; q < CRF_WORDS; ++q) {
             unsigned long long w = p.term[q];
             if (q == k) w &= ~(lanes_below(lane) | (1ull << lane));
             if (!found && w) { found = true; e = 64 * q + __builtin_ctzll(w); }
@@ -291,16 +240,16 @@ __device__ __forceinline__ void post_log_body(const PostArgs& a, const PostLds p
     }
     if (ent) {
         __syncthreads();   // block = one wave: the per-position scalars are in LDS
-        float r[PW];
+        float r[CRF_WORDS];
 #pragma unroll
-        for (int k = 0; k < PW; ++k) {
+        for (int k = 0; k < CRF_WORDS; ++k) {
             const int q = 64 * k + j;
             r[k] = 0.f;
             if (q >= 1 && q < L) r[k] = clamp_r(s_T[p.y[q - 1] * C + p.y[q]] + p.g[q] + p.bh[q] - p.bh[q - 1]);
         }
         __syncthreads();   // block = one wave: every g is read before it is overwritten
 #pragma unroll
-        for (int k = 0; k < PW; ++k) {
+        for (int k = 0; k < CRF_WORDS; ++k) {
             const int q = 64 * k + j;
             if (q < L) p.g[q] = r[k];
         }
@@ -427,9 +376,9 @@ __device__ __forceinline__ bool post_lin_body(const PostArgs& a, const PostLds p
     if (ent) {
         __syncthreads();   // block = one wave: the per-position scalars are in LDS
         // r_i = log(E[y_{i-1}][y_i] (x_i[y_i] / c_i) bhat_i[y_i] / bhat_{i-1}[y_{i-1}]): the logs beside the chains, lanes over i
-        float r[PW];
+        float r[CRF_WORDS];
 #pragma unroll
-        for (int k = 0; k < PW; ++k) {
+        for (int k = 0; k < CRF_WORDS; ++k) {
             const int q = 64 * k + j;
             r[k] = 0.f;
             if (q >= 1 && q < L)
@@ -437,7 +386,7 @@ __device__ __forceinline__ bool post_lin_body(const PostArgs& a, const PostLds p
         }
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < PW; ++k) {
+        for (int k = 0; k < CRF_WORDS; ++k) {
             const int q = 64 * k + j;
             if (q < L) p.g[q] = r[k];
         }
@@ -452,17 +401,17 @@ __device__ __forceinline__ bool post_lin_body(const PostArgs& a, const PostLds p
 __global__ __launch_bounds__(64) void crf_posterior_small_kernel(const PostArgs a) {
     __shared__ float s_buf[CRF_MAX_SC];   // scaled form: a_i[j] | x_i[j] (L * C <= 4096 each); log form: alpha_i[j]
     __shared__ float s_T[CM * CM], s_vec[64];
-    __shared__ float s_c[P_MAX_S], s_tc[P_MAX_S], s_bh[P_MAX_S], s_g[P_MAX_S];
-    __shared__ uint32_t s_w[P_MAX_S], s_table[P_MAX_L];
-    __shared__ unsigned long long s_term[PW];
-    __shared__ unsigned short s_pos[P_MAX_S];
-    __shared__ unsigned char s_y[P_MAX_S];
+    __shared__ float s_c[CRF_WORDS_MAX_S], s_tc[CRF_WORDS_MAX_S], s_bh[CRF_WORDS_MAX_S], s_g[CRF_WORDS_MAX_S];
+    __shared__ uint32_t s_w[CRF_WORDS_MAX_S], s_table[P_MAX_L];
+    __shared__ unsigned long long s_term[CRF_WORDS];
+    __shared__ unsigned short s_pos[CRF_WORDS_MAX_S];
+    __shared__ unsigned char s_y[CRF_WORDS_MAX_S];
     const int b = blockIdx.x, lane = threadIdx.x, S = a.S;
     if (a.table) s_table[lane] = lane < a.L_ids ? (uint32_t)a.table[lane] : LT_DEFAULT;
     // the on-positions, compacted in order: the rank of a position is the popcount of the ballots below it
     int L = 0;
 #pragma unroll
-    for (int k = 0; k < PW; ++k) {
+    for (int k = 0; k < CRF_WORDS; ++k) {
         const int t = 64 * k + lane;
         const bool on = t < S && on_pos(a, b, t);
         const unsigned long long km = __ballot(on);
@@ -485,9 +434,9 @@ __global__ __launch_bounds__(64) void crf_posterior_small_kernel(const PostArgs 
 __global__ __launch_bounds__(64) void crf_posterior_kernel(const PostArgs a) {
     __shared__ float s_buf[CRF_MAX_SC];
     __shared__ float s_T[64 * 64], s_vec[64];
-    __shared__ float s_tc[P_MAX_S], s_bh[P_MAX_S], s_g[P_MAX_S];
-    __shared__ uint32_t s_w[P_MAX_S], s_table[P_MAX_L];
-    __shared__ unsigned long long s_term[PW];
+    __shared__ float s_tc[CRF_WORDS_MAX_S], s_bh[CRF_WORDS_MAX_S], s_g[CRF_WORDS_MAX_S];
+    __shared__ uint32_t s_w[CRF_WORDS_MAX_S], s_table[P_MAX_L];
+    __shared__ unsigned long long s_term[CRF_WORDS];
     __shared__ unsigned char s_y[CRF_MAX_SC];
     const int b = blockIdx.x, lane = threadIdx.x, S = a.S;
     if (a.table) s_table[lane] = lane < a.L_ids ? (uint32_t)a.table[lane] : LT_DEFAULT;
@@ -519,14 +468,14 @@ extern "C" int icka_crf_posterior(const float* emissions, int64_t ld, const int6
     if (label_table && (!lens || !ent || !ent_conf || !n_ent)) return ICKA_E_ARG;
     if (B <= 0 || S <= 0 || C <= 0 || C > 64) return ICKA_E_SHAPE;
     if ((int64_t)S * C > CRF_MAX_SC || B > CRF_FLAT_MAX_B) return ICKA_E_SHAPE;
-    if (label_table && (S > P_MAX_S || L_ids <= 0 || L_ids > P_MAX_L)) return ICKA_E_SHAPE;
+    if (label_table && (S > CRF_WORDS_MAX_S || L_ids <= 0 || L_ids > P_MAX_L)) return ICKA_E_SHAPE;
     PostArgs a{};
     a.e = emissions; a.ld = ld; a.mask = mask; a.start = start; a.end = end; a.trans = trans;
     a.lens = lens; a.flat = tags_flat; a.cap = capacity; a.table = label_table; a.L_ids = L_ids;
     a.log_z = log_z; a.seq_logp = lens ? seq_logp : nullptr; a.token_conf = lens ? token_conf : nullptr; a.marg = marginals;
     a.ent = ent; a.ent_conf = ent_conf; a.n_ent = label_table ? n_ent : nullptr; a.bad = bad;
     a.B = B; a.S = S; a.C = C;
-    if (C <= CM && S <= P_MAX_S) hipLaunchKernelGGL(crf_posterior_small_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
+    if (C <= CM && S <= CRF_WORDS_MAX_S) hipLaunchKernelGGL(crf_posterior_small_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(crf_posterior_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
     ICKA_CHECK_LAUNCH();
     return 0;

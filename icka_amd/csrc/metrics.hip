@@ -14,7 +14,7 @@
 //   3. Per-type counts go through LDS atomics, then one 64-bit global atomic add per non-zero counter: integer sums, so the
 //      table does not depend on the order of the blocks and a graph replay equals an eager call exactly.
 // No host sync, no allocation: capturable.
-#include "common.h"
+#include "crf_core.h"
 
 namespace {
 
@@ -24,8 +24,7 @@ constexpr int CE_MAX_L = 64;           // tag ids (the CRF's own cap)
 constexpr int CE_MAX_TYPES = 32;
 constexpr int CE_HEAD = 6;             // kept_tokens, equal_tokens, correct_preds, total_preds, total_correct, bad_ids
 
-// label_table word of a tag id: these bits, the type id from bit 8 up
-constexpr uint32_t LT_DEFAULT = 1u, LT_BEGIN = 2u, LT_SKIP = 4u;
+// label_table word of a tag id: the bits LT_DEFAULT / LT_BEGIN / LT_SKIP (crf_core.h), the type id from bit 8 up
 
 struct ChunkEvalArgs {
     const int32_t* lens; const int32_t* flat; int64_t capacity;   // form (a): the paths back to back
@@ -36,18 +35,8 @@ struct ChunkEvalArgs {
     int B, S, L, ntypes;
 };
 
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
 __device__ __forceinline__ void add_counter(unsigned long long* p, unsigned long long v) {
     if (v) atomicAdd(p, v);
-}
-
-// start / term of position i of a compacted sequence from its word and the word before it
-__device__ __forceinline__ void chunk_flags(uint32_t w, uint32_t wp, bool first, bool in, bool& start, bool& term) {
-    const bool o = (w & LT_DEFAULT) != 0;
-    const bool po = (wp & LT_DEFAULT) != 0;
-    start = in && !o && (first || po || (w >> 8) != (wp >> 8) || (w & LT_BEGIN) != 0);
-    term = in && (o || start);
 }
 
 __global__ __launch_bounds__(64) void chunk_eval_kernel(const ChunkEvalArgs a) {

@@ -1037,6 +1037,55 @@ def check_flat_tags(lens, tags_flat, B, S):
 
 
 CRF_MAX_SC, CRF_POSTERIOR_MAX_S, CRF_POSTERIOR_MAX_IDS = 12288, 512, 64
+CRF_NBEST_MAX_C, CRF_NBEST_MAX_K, CRF_NBEST_MAX_S, CRF_NBEST_MAX_SCK = 16, 8, 512, 49152
+
+
+class _CrfOperands(object):
+    """The host-side checks of crf_posterior, crf_nbest and the crf_constrained_* entries, in the one order they all keep: the
+    four f32 parameters, ``emissions`` [B,S,C] and the transition shapes (the constructor); then the entry's own limits and its
+    operands (``vec`` / ``opt``) in the order the entry states them; the devices last (``same_device``).  ValueError for dtype /
+    shape / contiguity / a limit, then TypeError for an operand that is not on the device, before anything is launched."""
+
+    def __init__(self, who, emissions, start, end, trans):
+        for n, t in (("emissions", emissions), ("start", start), ("end", end), ("trans", trans)):
+            if not isinstance(t, torch.Tensor) or t.dtype != F32 or not t.is_contiguous():
+                raise ValueError("%s: %s must be contiguous f32" % (who, n))
+        if emissions.dim() != 3:
+            raise ValueError("%s: emissions must be [B,S,C], got %s" % (who, tuple(emissions.shape)))
+        Cn = emissions.shape[2]
+        if start.numel() != Cn or end.numel() != Cn or tuple(trans.shape) != (Cn, Cn):
+            raise ValueError("%s: transition parameters do not match num_tags = %d" % (who, Cn))
+        self.who, self.shape, self.used = who, tuple(emissions.shape), [emissions, start, end, trans]
+
+    def vec(self, t, name, dtype, shape=None, least=None, fits=None, what=None):
+        """``t`` must be a contiguous ``dtype`` tensor of exactly ``shape``, or of at least ``least[0]`` rows of the trailing
+        shape ``least[1:]``, or one that ``fits(t)``, worded by ``what``; it joins the operands of the device check."""
+        ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
+        if ok and shape is not None:
+            ok = tuple(t.shape) == shape
+        if ok and least is not None:
+            ok = t.dim() == len(least) and t.shape[0] >= least[0] and tuple(t.shape[1:]) == tuple(least[1:])
+        if ok and fits is not None:
+            ok = fits(t)
+        if not ok:
+            if what is None:
+                want = shape if shape is not None else (">= %d" % least[0],) + tuple(least[1:])
+                what = "a contiguous %s tensor of shape %s" % (dtype, want)
+            raise ValueError("%s: %s must be %s, got %s %s"
+                             % (self.who, name, what, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
+        self.used.append(t)
+        return t
+
+    def opt(self, t, *args, **kw):
+        """``vec`` of an operand that may be None."""
+        return None if t is None else self.vec(t, *args, **kw)
+
+    def same_device(self):
+        dev = self.used[0].device
+        for t in self.used:
+            _dev(t, "%s operand" % self.who)
+            if t.device != dev:
+                raise ValueError("%s: operands on %s and %s" % (self.who, dev, t.device))
 
 
 def crf_posterior(emissions, mask, start, end, trans, log_z, bad, *, lens=None, tags_flat=None, seq_logp=None,
@@ -1046,57 +1095,36 @@ def crf_posterior(emissions, mask, start, end, trans, log_z, bad, *, lens=None, 
     (icka_crf_posterior, include/icka_hip.h): one launch, no host sync.  ``bad`` (int32 [1]) is ADDED to: zero it first.
     Every operand is checked on the host (dtype, shape, contiguity, the kernel's limits: ValueError; then the device:
     TypeError) before anything is launched."""
-    def vec(t, name, dtype, shape=None, least=None):
-        ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
-        if ok and shape is not None:
-            ok = tuple(t.shape) == shape
-        if ok and least is not None:      # at least least[0] rows of the trailing shape least[1:]
-            ok = t.dim() == len(least) and t.shape[0] >= least[0] and tuple(t.shape[1:]) == tuple(least[1:])
-        if not ok:
-            want = shape if shape is not None else (">= %d" % least[0],) + tuple(least[1:])
-            raise ValueError("crf_posterior: %s must be a contiguous %s tensor of shape %s, got %s %s"
-                             % (name, dtype, want, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
-        return t
-
-    for n, t in (("emissions", emissions), ("start", start), ("end", end), ("trans", trans)):
-        if not isinstance(t, torch.Tensor) or t.dtype != F32 or not t.is_contiguous():
-            raise ValueError("crf_posterior: %s must be contiguous f32" % n)
-    if emissions.dim() != 3:
-        raise ValueError("crf_posterior: emissions must be [B,S,C], got %s" % (tuple(emissions.shape),))
-    B, S, Cn = emissions.shape
-    if start.numel() != Cn or end.numel() != Cn or tuple(trans.shape) != (Cn, Cn):
-        raise ValueError("crf_posterior: transition parameters do not match num_tags = %d" % Cn)
+    ops = _CrfOperands("crf_posterior", emissions, start, end, trans)
+    B, S, Cn = ops.shape
     if B < 1 or S < 1 or not 1 <= Cn <= 64 or S * Cn > CRF_MAX_SC or B > CRF_FLAT_MAX_B:
         raise ValueError("crf_posterior: B <= %d, C <= 64 and S * C <= %d, got [%d, %d, %d]"
                          % (CRF_FLAT_MAX_B, CRF_MAX_SC, B, S, Cn))
-    used = [emissions, start, end, trans, vec(log_z, "log_z", F32, (B,)), vec(bad, "bad", torch.int32, (1,))]
-    if mask is not None:
-        used.append(vec(mask, "mask", torch.int64, (B, S)))
-    if marginals is not None:
-        used.append(vec(marginals, "marginals", F32, (B, S, Cn)))
+    ops.vec(log_z, "log_z", F32, (B,))
+    ops.vec(bad, "bad", torch.int32, (1,))
+    ops.opt(mask, "mask", torch.int64, (B, S))
+    ops.opt(marginals, "marginals", F32, (B, S, Cn))
     if (lens is None) != (tags_flat is None):
         raise ValueError("crf_posterior: lens and tags_flat go together")
     cap, L_ids = 0, 0
     if lens is not None:
-        used += [vec(lens, "lens", torch.int32, (B,)), vec(tags_flat, "tags_flat", torch.int32, least=(0,))]
-        cap = tags_flat.numel()
-        used += [vec(seq_logp, "seq_logp", F32, (B,)), vec(token_conf, "token_conf", F32, least=(cap,))]
+        ops.vec(lens, "lens", torch.int32, (B,))
+        cap = ops.vec(tags_flat, "tags_flat", torch.int32, least=(0,)).numel()
+        ops.vec(seq_logp, "seq_logp", F32, (B,))
+        ops.vec(token_conf, "token_conf", F32, least=(cap,))
     elif seq_logp is not None or token_conf is not None or label_table is not None:
         raise ValueError("crf_posterior: seq_logp, token_conf and label_table need the paths (lens + tags_flat)")
     if label_table is not None:
-        vec(label_table, "label_table", torch.int32, least=(1,))
-        L_ids = label_table.numel()
+        L_ids = ops.vec(label_table, "label_table", torch.int32, least=(1,)).numel()
         if L_ids > CRF_POSTERIOR_MAX_IDS or S > CRF_POSTERIOR_MAX_S:
             raise ValueError("crf_posterior: with a label table at most %d words and S <= %d, got %d words, S = %d"
                              % (CRF_POSTERIOR_MAX_IDS, CRF_POSTERIOR_MAX_S, L_ids, S))
-        used += [label_table, vec(ent, "ent", torch.int32, least=(cap, 3)), vec(ent_conf, "ent_conf", F32, least=(cap,)),
-                 vec(n_ent, "n_ent", torch.int32, (B,))]
+        ops.vec(ent, "ent", torch.int32, least=(cap, 3))
+        ops.vec(ent_conf, "ent_conf", F32, least=(cap,))
+        ops.vec(n_ent, "n_ent", torch.int32, (B,))
     elif ent is not None or ent_conf is not None or n_ent is not None:
         raise ValueError("crf_posterior: ent, ent_conf and n_ent need a label_table")
-    for t in used:
-        _dev(t, "crf_posterior operand")
-        if t.device != emissions.device:
-            raise ValueError("crf_posterior: operands on %s and %s" % (emissions.device, t.device))
+    ops.same_device()
     check(_lib.load().icka_crf_posterior(emissions.data_ptr(), Cn, _ptr(mask), start.data_ptr(), end.data_ptr(),
                                          trans.data_ptr(), _ptr(lens), _ptr(tags_flat), cap, _ptr(label_table), L_ids,
                                          log_z.data_ptr(), _ptr(seq_logp), _ptr(token_conf), _ptr(marginals), _ptr(ent),
@@ -1104,28 +1132,13 @@ def crf_posterior(emissions, mask, start, end, trans, log_z, bad, *, lens=None, 
           "icka_crf_posterior")
 
 
-CRF_NBEST_MAX_C, CRF_NBEST_MAX_K, CRF_NBEST_MAX_S, CRF_NBEST_MAX_SCK = 16, 8, 512, 49152
-
-
 def crf_nbest(emissions, mask, start, end, trans, nbest, lens, n_paths, scores, tags_flat):
     """The ``nbest`` best tag paths of every sample (icka_crf_nbest, include/icka_hip.h): ``lens`` and ``n_paths`` int32 [B],
     ``scores`` f32 [B, nbest], ``tags_flat`` int32 [nbest, capacity >= B*S] (row r: rank r in the layout of
     ``crf_score_decode``).  One launch, no host sync.  Every operand is checked on the host (dtype, shape, contiguity, the
     kernel's limits: ValueError; then the device: TypeError) before anything is launched."""
-    def vec(t, name, dtype, shape):
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError("crf_nbest: %s must be a contiguous %s tensor of shape %s, got %s %s"
-                             % (name, dtype, shape, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
-        return t
-
-    for n, t in (("emissions", emissions), ("start", start), ("end", end), ("trans", trans)):
-        if not isinstance(t, torch.Tensor) or t.dtype != F32 or not t.is_contiguous():
-            raise ValueError("crf_nbest: %s must be contiguous f32" % n)
-    if emissions.dim() != 3:
-        raise ValueError("crf_nbest: emissions must be [B,S,C], got %s" % (tuple(emissions.shape),))
-    B, S, Cn = emissions.shape
-    if start.numel() != Cn or end.numel() != Cn or tuple(trans.shape) != (Cn, Cn):
-        raise ValueError("crf_nbest: transition parameters do not match num_tags = %d" % Cn)
+    ops = _CrfOperands("crf_nbest", emissions, start, end, trans)
+    B, S, Cn = ops.shape
     if isinstance(nbest, bool) or not isinstance(nbest, int):
         raise ValueError("crf_nbest: nbest must be an int, got %s" % type(nbest).__name__)
     if not 1 <= Cn <= CRF_NBEST_MAX_C:
@@ -1138,44 +1151,24 @@ def crf_nbest(emissions, mask, start, end, trans, nbest, lens, n_paths, scores, 
     if S * Cn * nbest > CRF_NBEST_MAX_SCK:
         raise ValueError("crf_nbest: S * num_tags * nbest <= %d (one back-pointer byte each), got %d * %d * %d = %d"
                          % (CRF_NBEST_MAX_SCK, S, Cn, nbest, S * Cn * nbest))
-    used = [emissions, start, end, trans, vec(lens, "lens", torch.int32, (B,)), vec(n_paths, "n_paths", torch.int32, (B,)),
-            vec(scores, "scores", F32, (B, nbest))]
-    if mask is not None:
-        used.append(vec(mask, "mask", torch.int64, (B, S)))
-    if not (isinstance(tags_flat, torch.Tensor) and tags_flat.dtype == torch.int32 and tags_flat.is_contiguous()
-            and tags_flat.dim() == 2 and tags_flat.shape[0] == nbest and tags_flat.shape[1] >= B * S):
-        raise ValueError("crf_nbest: tags_flat must be a contiguous int32 tensor of shape (%d, >= %d), got %s %s"
-                         % (nbest, B * S, getattr(tags_flat, "dtype", type(tags_flat).__name__),
-                            tuple(getattr(tags_flat, "shape", ()))))
-    used.append(tags_flat)
-    for t in used:
-        _dev(t, "crf_nbest operand")
-        if t.device != emissions.device:
-            raise ValueError("crf_nbest: operands on %s and %s" % (emissions.device, t.device))
+    ops.vec(lens, "lens", torch.int32, (B,))
+    ops.vec(n_paths, "n_paths", torch.int32, (B,))
+    ops.vec(scores, "scores", F32, (B, nbest))
+    ops.opt(mask, "mask", torch.int64, (B, S))
+    ops.vec(tags_flat, "tags_flat", torch.int32,
+            fits=lambda t: t.dim() == 2 and t.shape[0] == nbest and t.shape[1] >= B * S,
+            what="a contiguous int32 tensor of shape (%d, >= %d)" % (nbest, B * S))
+    ops.same_device()
     check(_lib.load().icka_crf_nbest(emissions.data_ptr(), Cn, _ptr(mask), start.data_ptr(), end.data_ptr(),
                                      trans.data_ptr(), nbest, lens.data_ptr(), n_paths.data_ptr(), scores.data_ptr(),
                                      tags_flat.data_ptr(), tags_flat.shape[1], B, S, Cn, _stream()),
           "icka_crf_nbest")
 
 
-def _crf_constrained_check(who, emissions, mask, allowed, start, end, trans, extra, flat_b=False):
-    """The host-side checks shared by the three constrained-CRF entries -> (B, S, C).  ``extra``: (tensor, name, dtype, shape)
-    of the entry's own operands (a None tensor is skipped).  ValueError for dtype / shape / contiguity / the kernel's limits,
-    then TypeError for an operand that is not on the device, before anything is launched."""
-    def vec(t, name, dtype, shape):
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError("%s: %s must be a contiguous %s tensor of shape %s, got %s %s"
-                             % (who, name, dtype, shape, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
-        return t
-
-    for n, t in (("emissions", emissions), ("start", start), ("end", end), ("trans", trans)):
-        if not isinstance(t, torch.Tensor) or t.dtype != F32 or not t.is_contiguous():
-            raise ValueError("%s: %s must be contiguous f32" % (who, n))
-    if emissions.dim() != 3:
-        raise ValueError("%s: emissions must be [B,S,C], got %s" % (who, tuple(emissions.shape)))
-    B, S, Cn = emissions.shape
-    if start.numel() != Cn or end.numel() != Cn or tuple(trans.shape) != (Cn, Cn):
-        raise ValueError("%s: transition parameters do not match num_tags = %d" % (who, Cn))
+def _crf_constrained_operands(who, emissions, mask, allowed, start, end, trans, flat_b=False):
+    """What the three constrained-CRF entries check before their own operands: the limits, ``allowed`` and ``mask``."""
+    ops = _CrfOperands(who, emissions, start, end, trans)
+    B, S, Cn = ops.shape
     if not 1 <= Cn <= 64:
         raise ValueError("%s: 1 <= num_tags <= 64 (one lane and one bit per tag), got %d" % (who, Cn))
     if B < 1 or S < 1:
@@ -1184,27 +1177,9 @@ def _crf_constrained_check(who, emissions, mask, allowed, start, end, trans, ext
         raise ValueError("%s: S * num_tags <= %d, got %d * %d = %d" % (who, CRF_MAX_SC, S, Cn, S * Cn))
     if flat_b and B > CRF_FLAT_MAX_B:
         raise ValueError("%s: B <= %d (the kernel sums the path offsets itself), got %d" % (who, CRF_FLAT_MAX_B, B))
-    used = [emissions, start, end, trans, vec(allowed, "allowed", torch.int64, (B, S))]
-    if mask is not None:
-        used.append(vec(mask, "mask", torch.int64, (B, S)))
-    for t, name, dtype, shape in extra:
-        shape = shape(B, S, Cn) if callable(shape) else shape
-        if t is None:
-            continue
-        if shape[0] == "at least":           # 1-D with room for shape[1] entries
-            if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.dim() == 1
-                    and t.numel() >= shape[1]):
-                raise ValueError("%s: %s must be a contiguous 1-D %s tensor of at least %d entries, got %s %s"
-                                 % (who, name, dtype, shape[1], getattr(t, "dtype", type(t).__name__),
-                                    tuple(getattr(t, "shape", ()))))
-            used.append(t)
-        else:
-            used.append(vec(t, name, dtype, shape))
-    for t in used:
-        _dev(t, "%s operand" % who)
-        if t.device != emissions.device:
-            raise ValueError("%s: operands on %s and %s" % (who, emissions.device, t.device))
-    return B, S, Cn
+    ops.vec(allowed, "allowed", torch.int64, (B, S))
+    ops.opt(mask, "mask", torch.int64, (B, S))
+    return ops
 
 
 def crf_constrained_llh(emissions, mask, allowed, start, end, trans, llh, log_z, log_za, infeasible=None):
@@ -1212,10 +1187,12 @@ def crf_constrained_llh(emissions, mask, allowed, start, end, trans, llh, log_z,
     ``log_za`` and ``log_z`` (icka_crf_constrained_llh, include/icka_hip.h).  ``infeasible`` (int32 [1] or None) is ADDED to:
     zero it first.  One launch, no host sync."""
     who = "crf_constrained_llh"
-    B, S, Cn = _crf_constrained_check(who, emissions, mask, allowed, start, end, trans,
-                                      [(llh, "llh", F32, lambda B, S, C: (B,)), (log_z, "log_z", F32, lambda B, S, C: (B,)),
-                                       (log_za, "log_za", F32, lambda B, S, C: (B,)),
-                                       (infeasible, "infeasible", torch.int32, (1,))])
+    ops = _crf_constrained_operands(who, emissions, mask, allowed, start, end, trans)
+    B, S, Cn = ops.shape
+    for t, name in ((llh, "llh"), (log_z, "log_z"), (log_za, "log_za")):
+        ops.opt(t, name, F32, (B,))
+    ops.opt(infeasible, "infeasible", torch.int32, (1,))
+    ops.same_device()
     if llh is None or log_z is None or log_za is None:
         raise ValueError("%s: llh, log_z and log_za are all written" % who)
     check(_lib.load().icka_crf_constrained_llh(emissions.data_ptr(), Cn, _ptr(mask), allowed.data_ptr(), start.data_ptr(),
@@ -1229,12 +1206,12 @@ def crf_constrained_grad(emissions, mask, allowed, start, end, trans, gllh, d_em
     """``gllh[b] * d llh[b] / d(.)`` of ``crf_constrained_llh``: ``d_emissions`` [B,S,C] is written, ``d_start``, ``d_end`` and
     ``d_trans`` are ADDED to with atomics (the contract of ``crf_grad``).  One launch, no host sync."""
     who = "crf_constrained_grad"
-    bsc = lambda B, S, C: (B, S, C)
-    B, S, Cn = _crf_constrained_check(who, emissions, mask, allowed, start, end, trans,
-                                      [(gllh, "gllh", F32, lambda B, S, C: (B,)), (d_emissions, "d_emissions", F32, bsc),
-                                       (d_start, "d_start", F32, lambda B, S, C: (C,)),
-                                       (d_end, "d_end", F32, lambda B, S, C: (C,)),
-                                       (d_trans, "d_trans", F32, lambda B, S, C: (C, C))])
+    ops = _crf_constrained_operands(who, emissions, mask, allowed, start, end, trans)
+    B, S, Cn = ops.shape
+    for t, name, shape in ((gllh, "gllh", (B,)), (d_emissions, "d_emissions", (B, S, Cn)), (d_start, "d_start", (Cn,)),
+                           (d_end, "d_end", (Cn,)), (d_trans, "d_trans", (Cn, Cn))):
+        ops.opt(t, name, F32, shape)
+    ops.same_device()
     if any(t is None for t in (gllh, d_emissions, d_start, d_end, d_trans)):
         raise ValueError("%s: gllh and the four gradients are all needed" % who)
     check(_lib.load().icka_crf_constrained_grad(emissions.data_ptr(), Cn, _ptr(mask), allowed.data_ptr(), start.data_ptr(),
@@ -1248,11 +1225,14 @@ def crf_constrained_decode(emissions, mask, allowed, start, end, trans, lens, ta
     [B], ``tags_flat`` int32 [>= B*S] in the layout of ``crf_score_decode``, ``scores`` f32 [B]; an infeasible sample holds -1
     tags and a -inf score and adds 1 to ``infeasible`` (int32 [1] or None; zero it first).  One launch, no host sync."""
     who = "crf_constrained_decode"
-    B, S, Cn = _crf_constrained_check(who, emissions, mask, allowed, start, end, trans,
-                                      [(lens, "lens", torch.int32, lambda B, S, C: (B,)),
-                                       (tags_flat, "tags_flat", torch.int32, lambda B, S, C: ("at least", B * S)),
-                                       (scores, "scores", F32, lambda B, S, C: (B,)),
-                                       (infeasible, "infeasible", torch.int32, (1,))], flat_b=True)
+    ops = _crf_constrained_operands(who, emissions, mask, allowed, start, end, trans, flat_b=True)
+    B, S, Cn = ops.shape
+    ops.opt(lens, "lens", torch.int32, (B,))
+    ops.opt(tags_flat, "tags_flat", torch.int32, fits=lambda t: t.dim() == 1 and t.numel() >= B * S,
+            what="a contiguous 1-D %s tensor of at least %d entries" % (torch.int32, B * S))
+    ops.opt(scores, "scores", F32, (B,))
+    ops.opt(infeasible, "infeasible", torch.int32, (1,))
+    ops.same_device()
     if lens is None or scores is None or tags_flat is None:
         raise ValueError("%s: lens, tags_flat and scores are all written" % who)
     check(_lib.load().icka_crf_constrained_decode(emissions.data_ptr(), Cn, _ptr(mask), allowed.data_ptr(), start.data_ptr(),
