@@ -165,6 +165,10 @@ PROTOTYPES = {
                                           c_i32, c_i32, c_vp]),
     "icka_crf_constrained_decode": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32,
                                             c_i32, c_i32, c_vp]),
+    "icka_crf_expect": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32,
+                                c_i32, c_i32, c_vp]),
+    "icka_crf_expect_grad": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
+                                     c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "icka_chunk_eval": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "icka_loss_accumulate": (c_i32, [c_vp, c_vp, c_vp]),
     "icka_attn_bwd":(c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,

@@ -161,6 +161,72 @@ class _CrfConstrainedFn(torch.autograd.Function):
         return None, de, None, None, None, None
 
 
+class _ExpectCfg(object):
+    """What one ``_CrfExpectFn`` call is asked for.  ``relative``: the payoff mode of icka_crf_expect; ``want_expect``: False
+    computes log Z only; ``other`` / ``A_other``: the CRF (and its arena) whose three parameters are the second lattice's, or
+    None when those parts are plain tensors; ``first_grad`` / ``second_grad``: whether that lattice is differentiated."""
+
+    def __init__(self, relative, want_expect, other=None, A_other=None, first_grad=True, second_grad=True):
+        self.relative, self.want_expect, self.other, self.A_other = relative, want_expect, other, A_other
+        self.first_grad, self.second_grad = first_grad, second_grad
+
+
+def _params(mod):
+    return (mod.start_transitions.detach(), mod.end_transitions.detach(), mod.transitions.detach())
+
+
+class _CrfExpectFn(torch.autograd.Function):
+    """``(log Z_p, E_p[r])`` per sample (icka_crf_expect / _grad): one launch forward, one backward.  The gradients of a CRF
+    module's own parameters -- the first lattice's and, with ``cfg.other``, the second's -- are added into the arena as in
+    ``_CrfFn``; payoff parts given as plain tensors get theirs through autograd from freshly zeroed buffers."""
+
+    @staticmethod
+    def forward(ctx, anchor, emissions, mask, mod, A: ParamArena, cfg: _ExpectCfg, second, second_start, second_end,
+                second_trans):
+        B = emissions.shape[0]
+        out = torch.empty(2 if cfg.want_expect else 1, B, dtype=F32, device=emissions.device)     # log Z | E[r]
+        if cfg.other is not None:
+            second_start, second_end, second_trans = _params(cfg.other)
+        K.crf_expect(emissions, mask, *_params(mod), out[0], out[1] if cfg.want_expect else None, second=second,
+                     second_start=second_start, second_end=second_end, second_trans=second_trans, relative=cfg.relative)
+        ctx.mod, ctx.A, ctx.cfg = mod, A, cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(emissions, mask, second, second_start, second_end, second_trans)
+        return out[0], (out[1] if cfg.want_expect else None)
+
+    @staticmethod
+    def backward(ctx, g_logz, g_expect):
+        emissions, mask, second, s_start, s_end, s_trans = ctx.saved_tensors
+        cfg = ctx.cfg
+        none = (None,) * 10
+        g_logz = None if g_logz is None else g_logz.to(F32).contiguous()
+        g_expect = None if g_expect is None else g_expect.to(F32).contiguous()
+        if g_logz is None and g_expect is None:
+            return none
+        de, gs = None, (None, None, None)
+        if cfg.first_grad:
+            _, gs = _grads_for_atomics(ctx.mod, ctx.A)
+            de = torch.empty_like(emissions)
+        d2, gs2 = None, (None, None, None)
+        if cfg.second_grad and g_expect is not None:
+            if second is not None and ctx.needs_input_grad[6]:
+                d2 = torch.empty_like(second)
+            if cfg.other is not None:
+                _, gs2 = _grads_for_atomics(cfg.other, cfg.A_other)
+            else:
+                gs2 = tuple(torch.zeros_like(t) if t is not None and ctx.needs_input_grad[7 + n] else None
+                            for n, t in enumerate((s_start, s_end, s_trans)))
+        K.crf_expect_grad(emissions, mask, *_params(ctx.mod), g_logz, g_expect, de, *gs, second=second, second_start=s_start,
+                          second_end=s_end, second_trans=s_trans, relative=cfg.relative, d_second=d2, d_second_start=gs2[0],
+                          d_second_end=gs2[1], d_second_trans=gs2[2])
+        if cfg.first_grad:
+            ctx.A.flush_final()
+        if cfg.other is not None and gs2[0] is not None:
+            cfg.A_other.flush_final()
+            gs2 = (None, None, None)      # the arena holds them: nothing goes through autograd
+        return (None, de, None, None, None, None, d2) + tuple(gs2)
+
+
 class CRF(ArenaModule):
     def __init__(self, num_tags: int, batch_first: bool = False) -> None:
         if num_tags <= 0:
@@ -471,6 +537,125 @@ class CRF(ArenaModule):
         K.crf_constrained_decode(e, m, al, self.start_transitions.detach(), self.end_transitions.detach(),
                                  self.transitions.detach(), out.tags.lens, out.tags.tags_flat, out.scores, out.infeasible)
         return out
+
+    # ----------------------------------------------------------------------------------------------- expectations
+    def _prep_expect(self, who: str, emissions, mask):
+        """(e, m) batch-first with position 0 of the mask forced on, inside the limit of icka_crf_expect."""
+        e, _, m = self._prep(emissions, None, mask)
+        S = e.shape[1]
+        if S * self.num_tags > K.CRF_EXPECT_MAX_SC:
+            raise ValueError("%s: S * num_tags <= %d, got %d * %d = %d"
+                             % (who, K.CRF_EXPECT_MAX_SC, S, self.num_tags, S * self.num_tags))
+        if m is not None:
+            m[:, 0] = 1            # (m is _prep's own copy) position 0 is on, as in posterior
+        return e, m
+
+    def _like_emissions(self, who: str, name: str, t, emissions) -> torch.Tensor:
+        """``t`` (a second [.., .., C] tensor in the layout of ``emissions``) as contiguous f32 [B,S,C]"""
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise ValueError("%s: %s must be a floating-point tensor, got %s"
+                             % (who, name, getattr(t, "dtype", type(t).__name__)))
+        if isinstance(emissions, torch.Tensor) and tuple(t.shape) != tuple(emissions.shape):
+            raise ValueError("%s: %s must have the shape of the emissions %s, got %s"
+                             % (who, name, tuple(emissions.shape), tuple(t.shape)))
+        if not self.batch_first:
+            t = t.transpose(0, 1)
+        return t.to(F32).contiguous()
+
+    def log_partition(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``log Z`` per sample, f32 [B], differentiable in ``emissions`` and the three parameters (icka_crf_expect / _grad:
+        one launch forward, one backward, no host sync).  The chain runs over position 0 and the positions with
+        ``mask != 0``, as in ``posterior``."""
+        e, m = self._prep_expect("CRF.log_partition", emissions, mask)
+        A = self._arena()
+        return _CrfExpectFn.apply(A.anchor, e, m, self, A, _ExpectCfg(True, False), None, None, None, None)[0]
+
+    def entropy(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None, reduction: str = "none") -> torch.Tensor:
+        """The entropy of the distribution over tag paths, ``H = log Z - E_p[score(y)]`` (>= 0, at most ``L log num_tags``):
+        the uncertainty measure of active learning and the entropy-minimisation term on unlabelled data.  Differentiable in
+        ``emissions`` and the three parameters: one launch forward, one backward, no host sync.  The chain runs over position
+        0 and the positions with ``mask != 0``, as in ``posterior``; reductions as in ``forward``.  Limit:
+        ``S * num_tags <= 4096``.  Constraints and packed batches are not covered."""
+        _check_reduction(reduction)
+        e, m = self._prep_expect("CRF.entropy", emissions, mask)
+        A = self._arena()
+        log_z, ex = _CrfExpectFn.apply(A.anchor, e, m, self, A, _ExpectCfg(True, True), None, None, None, None)
+        return self._reduce(log_z - ex, m, e, reduction)
+
+    def kl_divergence(self, emissions: torch.Tensor, other_emissions: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                      other: Optional["CRF"] = None, detach: str = "none", reduction: str = "none") -> torch.Tensor:
+        """``KL(p || q)`` between two CRF distributions over the tag paths of the same sentences: ``p`` is this module on
+        ``emissions``, ``q`` is ``other`` (a CRF with the same ``num_tags``; default: this module, two views through one CRF)
+        on ``other_emissions``.  Differentiable on both sides; ``detach="self"`` / ``"other"`` gives that side no gradient and
+        skips its gradient work (a detached teacher, a stop-gradient view).  Two launches forward and two backward
+        (``E_p[s_p - s_q]`` and ``log Z_p``, then ``log Z_q``), no host sync.  Mask, reductions and limits as in ``entropy``."""
+        who = "CRF.kl_divergence"
+        _check_reduction(reduction)
+        if detach not in ("none", "self", "other"):
+            raise ValueError("%s: detach must be 'none', 'self' or 'other', got %r" % (who, detach))
+        q = self if other is None else other
+        if not isinstance(q, CRF) or q.num_tags != self.num_tags:
+            raise ValueError("%s: other must be a CRF with num_tags = %d, got %s"
+                             % (who, self.num_tags, q if isinstance(q, CRF) else type(q).__name__))
+        e2 = self._like_emissions(who, "other_emissions", other_emissions, emissions)
+        if detach == "self" and isinstance(emissions, torch.Tensor):
+            emissions = emissions.detach()
+        if detach == "other":
+            e2 = e2.detach()
+        e, m = self._prep_expect(who, emissions, mask)
+        A, Aq = self._arena(), q._arena()
+        cfg = _ExpectCfg(True, True, other=q, A_other=Aq, first_grad=detach != "self", second_grad=detach != "other")
+        log_zp, ex = _CrfExpectFn.apply(A.anchor, e, m, self, A, cfg, e2, None, None, None)
+        if detach == "other":
+            log_zq = K.crf_expect(e2, m, *_params(q), torch.empty_like(log_zp))
+        else:
+            log_zq = _CrfExpectFn.apply(Aq.anchor, e2, m, q, Aq, _ExpectCfg(True, False), None, None, None, None)[0]
+        return self._reduce(ex - log_zp + log_zq, m, e, reduction)
+
+    def expected(self, emissions: torch.Tensor, payoff: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
+                 payoff_start: Optional[torch.Tensor] = None, payoff_end: Optional[torch.Tensor] = None,
+                 payoff_transitions: Optional[torch.Tensor] = None, reduction: str = "none") -> torch.Tensor:
+        """``E_p[r(y)]`` of a path-additive payoff: ``payoff`` in the layout of ``emissions`` scores tag j at position t,
+        ``payoff_start`` / ``payoff_end`` [num_tags] the first / last tag and ``payoff_transitions`` [num_tags, num_tags] every
+        transition (each optional: zeros).  Differentiable in ``emissions``, the three parameters and every payoff tensor
+        (those through ordinary autograd): one launch forward, one backward, no host sync.  Mask, reductions and limits as in
+        ``entropy``."""
+        who = "CRF.expected"
+        _check_reduction(reduction)
+        g = self._like_emissions(who, "payoff", payoff, emissions)
+        parts = []
+        for name, t, shape in (("payoff_start", payoff_start, (self.num_tags,)), ("payoff_end", payoff_end, (self.num_tags,)),
+                               ("payoff_transitions", payoff_transitions, (self.num_tags, self.num_tags))):
+            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_floating_point() or tuple(t.shape) != shape):
+                raise ValueError("%s: %s must be a floating-point tensor of shape %s, got %s %s"
+                                 % (who, name, shape, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
+            parts.append(None if t is None else t.to(F32).contiguous())
+        e, m = self._prep_expect(who, emissions, mask)
+        A = self._arena()
+        ex = _CrfExpectFn.apply(A.anchor, e, m, self, A, _ExpectCfg(False, True), g, *parts)[1]
+        return self._reduce(ex, m, e, reduction)
+
+    def expected_cost(self, emissions: torch.Tensor, tags: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                      cost: Optional[torch.Tensor] = None, reduction: str = "none") -> torch.Tensor:
+        """The expected cost of the model's tag path against ``tags``: ``sum_t E_p[cost[tags_t, y_t]]`` over the chain's
+        positions.  ``cost``: f32 [num_tags, num_tags] (gold, predicted); default ``1 - I``, the expected number of wrong tags
+        (minimum-risk training, a calibrated error estimate).  ``expected`` with ``payoff = cost[tags]``; tag ids are clamped
+        into [0, num_tags) where they are read, so positions that are off may carry pad labels."""
+        who = "CRF.expected_cost"
+        Cn = self.num_tags
+        if not isinstance(tags, torch.Tensor) or tags.is_floating_point() or tags.dtype == torch.bool:
+            raise ValueError("%s: tags must be an integer tensor, got %s" % (who, getattr(tags, "dtype", type(tags).__name__)))
+        if isinstance(emissions, torch.Tensor) and tuple(tags.shape) != tuple(emissions.shape[:2]):
+            raise ValueError("%s: the first two dimensions of emissions and tags must match, got %s and %s"
+                             % (who, tuple(emissions.shape[:2]), tuple(tags.shape)))
+        if cost is None:
+            cost = 1.0 - torch.eye(Cn, dtype=F32, device=tags.device)
+        elif not isinstance(cost, torch.Tensor) or cost.dtype != F32 or tuple(cost.shape) != (Cn, Cn):
+            raise ValueError("%s: cost must be an f32 tensor of shape %s, got %s %s"
+                             % (who, (Cn, Cn), getattr(cost, "dtype", type(cost).__name__), tuple(getattr(cost, "shape", ()))))
+        if cost.device != tags.device:
+            raise ValueError("%s: tags on %s, cost on %s" % (who, tags.device, cost.device))
+        return self.expected(emissions, cost[tags.to(torch.int64).clamp(0, Cn - 1)], mask, reduction=reduction)
 
 
 class _JointBuffer(object):

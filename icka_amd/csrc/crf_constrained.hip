@@ -28,7 +28,6 @@
 namespace {
 
 constexpr int ON_WORDS = CRF_MAX_SC / 64;   // S <= 12288 (C = 1): 64 positions per word
-typedef unsigned long long u64;
 
 struct ConArgs {
     const float* e; int64_t ld;
@@ -62,28 +61,6 @@ __device__ __forceinline__ int scan_sample(const ConArgs& a, int b, int lane, u6
     feasible = __ballot(bad) == 0ull;
     return L;
 }
-// the first on-position after t, or S (wave-uniform)
-__device__ __forceinline__ int next_on(const u64* s_on, int t, int S) {
-    const int q = t + 1;
-    if (q >= S) return S;
-    const int nw = (S + 63) >> 6;
-    int k = q >> 6;
-    u64 m = s_on[k] & (~0ull << (q & 63));
-    while (m == 0ull) {
-        if (++k >= nw) return S;
-        m = s_on[k];
-    }
-    return __builtin_amdgcn_readfirstlane(k * 64 + __builtin_ctzll(m));
-}
-// the last on-position before t >= 1 (position 0 is always on; wave-uniform)
-__device__ __forceinline__ int prev_on(const u64* s_on, int t) {
-    const int q = t - 1;
-    int k = q >> 6;
-    u64 m = s_on[k] & (~0ull >> (63 - (q & 63)));
-    while (m == 0ull && k > 0) m = s_on[--k];
-    return __builtin_amdgcn_readfirstlane(k * 64 + 63 - __builtin_clzll(m | 1ull));
-}
-
 // Forward recursion of the free (R = false) or the restricted lattice -> log Z (wave-uniform).  KEEP: alpha of on-position i
 // at s_al[i * C + j] (L * C floats); else two rows in turn.
 template <bool R, bool KEEP>

@@ -1,6 +1,6 @@
-// What the CRF kernels (crf.hip, crf_posterior.hip, crf_nbest.hip, crf_constrained.hip) and the chunk pass of metrics.hip
-// share: the limits of the entries, the label-table word bits with the chunk rule, and the 16-lane wave primitives of the
-// register / shuffle forms.  One definition each; everything is constexpr or forced inline.
+// What the CRF kernels (crf.hip, crf_posterior.hip, crf_nbest.hip, crf_constrained.hip, crf_expect.hip) and the chunk pass of metrics.hip
+// share: the limits of the entries, the label-table word bits with the chunk rule, the walk over a sample's on-positions and
+// the 16-lane wave primitives of the register / shuffle forms.  One definition each; everything is constexpr or forced inline.
 #pragma once
 #include "common.h"
 
@@ -8,6 +8,7 @@
 constexpr int CRF_MAX_SC = 12288;       // S * C per sample: floats of per-position scores (48 KiB) / bytes of back-pointers in LDS
 constexpr int CRF_FLAT_MAX_B = 2048;    // entries that write paths back to back: each wave sums the lengths of the samples before its own
 constexpr int CRF_LIN_SC = 4096;        // S * C of the scaled linear-domain form: a_t and x_t tiles of 16 KiB each
+constexpr int CRF_EXPECT_SC = CRF_LIN_SC;   // S * C of icka_crf_expect / _grad: alpha and centred-payoff tiles of 16 KiB each
 constexpr int CM = 16;                  // tags of the register / shuffle forms (the reference has 13 / 15 labels)
 constexpr int CRF_WORDS = 8;            // 64-position words of the kernels that keep a sample's positions on the lanes
 constexpr int CRF_WORDS_MAX_S = 64 * CRF_WORDS;   // S <= 512 there
@@ -32,6 +33,31 @@ __device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1u
 template <class A>
 __device__ __forceinline__ bool on_pos(const A& a, int b, int t) {
     return t == 0 || a.mask == nullptr || a.mask[(int64_t)b * a.S + t] != 0;
+}
+
+// The on-positions of a sample as a bit set in LDS, s_on[t / 64] bit t % 64 (bits at or past S clear): a recursion finds its
+// next position with a bit scan, so it can fetch that position's operands one step ahead.
+typedef unsigned long long u64;
+// the first on-position after t, or S (wave-uniform)
+__device__ __forceinline__ int next_on(const u64* s_on, int t, int S) {
+    const int q = t + 1;
+    if (q >= S) return S;
+    const int nw = (S + 63) >> 6;
+    int k = q >> 6;
+    u64 m = s_on[k] & (~0ull << (q & 63));
+    while (m == 0ull) {
+        if (++k >= nw) return S;
+        m = s_on[k];
+    }
+    return __builtin_amdgcn_readfirstlane(k * 64 + __builtin_ctzll(m));
+}
+// the last on-position before t >= 1 (position 0 is always on; wave-uniform)
+__device__ __forceinline__ int prev_on(const u64* s_on, int t) {
+    const int q = t - 1;
+    int k = q >> 6;
+    u64 m = s_on[k] & (~0ull >> (63 - (q & 63)));
+    while (m == 0ull && k > 0) m = s_on[--k];
+    return __builtin_amdgcn_readfirstlane(k * 64 + 63 - __builtin_clzll(m | 1ull));
 }
 
 // 16-lane row reductions on the DPP path (row_ror: no LDS crossbar, ~4 VALU ops): every lane of the row gets the result

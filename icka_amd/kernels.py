@@ -1242,6 +1242,76 @@ def crf_constrained_decode(emissions, mask, allowed, start, end, trans, lens, ta
           "icka_crf_constrained_decode")
 
 
+CRF_EXPECT_MAX_SC = 4096
+
+
+def _crf_expect_operands(who, emissions, mask, start, end, trans, second, second_start, second_end, second_trans, relative):
+    """What the two expectation entries check before their own operands: the limits, the mask, the second lattice, the mode."""
+    ops = _CrfOperands(who, emissions, start, end, trans)
+    B, S, Cn = ops.shape
+    if not 1 <= Cn <= 64:
+        raise ValueError("%s: 1 <= num_tags <= 64 (one lane per tag), got %d" % (who, Cn))
+    if B < 1 or S < 1:
+        raise ValueError("%s: empty batch [%d, %d, %d]" % (who, B, S, Cn))
+    if S * Cn > CRF_EXPECT_MAX_SC:
+        raise ValueError("%s: S * num_tags <= %d, got %d * %d = %d" % (who, CRF_EXPECT_MAX_SC, S, Cn, S * Cn))
+    if not isinstance(relative, bool):
+        raise ValueError("%s: relative must be a bool, got %s" % (who, type(relative).__name__))
+    ops.opt(mask, "mask", torch.int64, (B, S))
+    ops.opt(second, "second", F32, (B, S, Cn))
+    ops.opt(second_start, "second_start", F32, (Cn,))
+    ops.opt(second_end, "second_end", F32, (Cn,))
+    ops.opt(second_trans, "second_trans", F32, (Cn, Cn))
+    return ops
+
+
+def crf_expect(emissions, mask, start, end, trans, log_z, expect=None, *, second=None, second_start=None, second_end=None,
+               second_trans=None, relative=False):
+    """``log_z`` = log Z_p and ``expect`` = E_p[r(y)] per sample (icka_crf_expect, include/icka_hip.h): the payoff ``r`` is the
+    path score of the second lattice (every part nullable = zeros) or, with ``relative``, p's own score minus it.
+    ``expect=None`` computes ``log_z`` only.  One launch, no host sync.  Every operand is checked on the host (ValueError, then
+    TypeError for a wrong device) before anything is launched."""
+    who = "crf_expect"
+    ops = _crf_expect_operands(who, emissions, mask, start, end, trans, second, second_start, second_end, second_trans, relative)
+    B, S, Cn = ops.shape
+    ops.opt(log_z, "log_z", F32, (B,))
+    ops.opt(expect, "expect", F32, (B,))
+    ops.same_device()
+    if log_z is None:
+        raise ValueError("%s: log_z is always written" % who)
+    check(_lib.load().icka_crf_expect(emissions.data_ptr(), Cn, _ptr(mask), start.data_ptr(), end.data_ptr(), trans.data_ptr(),
+                                      _ptr(second), Cn, _ptr(second_start), _ptr(second_end), _ptr(second_trans),
+                                      int(relative), log_z.data_ptr(), _ptr(expect), B, S, Cn, _stream()),
+          "icka_crf_expect")
+    return log_z
+
+
+def crf_expect_grad(emissions, mask, start, end, trans, g_logz, g_expect, d_emissions, d_start, d_end, d_trans, *, second=None,
+                    second_start=None, second_end=None, second_trans=None, relative=False, d_second=None,
+                    d_second_start=None, d_second_end=None, d_second_trans=None):
+    """``g_logz[b] * d log_z[b] / d(.) + g_expect[b] * d expect[b] / d(.)`` of ``crf_expect`` for both lattices
+    (icka_crf_expect_grad): ``d_emissions`` and ``d_second`` [B,S,C] are written, the six parameter gradients are ADDED to with
+    atomics (the contract of ``crf_grad``).  Every one of the two upstream vectors and the eight outputs may be None: not
+    given / not wanted, its work is skipped.  One launch, no host sync."""
+    who = "crf_expect_grad"
+    ops = _crf_expect_operands(who, emissions, mask, start, end, trans, second, second_start, second_end, second_trans, relative)
+    B, S, Cn = ops.shape
+    for t, name, shape in ((g_logz, "g_logz", (B,)), (g_expect, "g_expect", (B,)),
+                           (d_emissions, "d_emissions", (B, S, Cn)), (d_start, "d_start", (Cn,)), (d_end, "d_end", (Cn,)),
+                           (d_trans, "d_trans", (Cn, Cn)), (d_second, "d_second", (B, S, Cn)),
+                           (d_second_start, "d_second_start", (Cn,)), (d_second_end, "d_second_end", (Cn,)),
+                           (d_second_trans, "d_second_trans", (Cn, Cn))):
+        ops.opt(t, name, F32, shape)
+    ops.same_device()
+    check(_lib.load().icka_crf_expect_grad(emissions.data_ptr(), Cn, _ptr(mask), start.data_ptr(), end.data_ptr(),
+                                           trans.data_ptr(), _ptr(second), Cn, _ptr(second_start), _ptr(second_end),
+                                           _ptr(second_trans), int(relative), _ptr(g_logz), _ptr(g_expect),
+                                           _ptr(d_emissions), Cn, _ptr(d_start), _ptr(d_end), _ptr(d_trans), _ptr(d_second),
+                                           Cn, _ptr(d_second_start), _ptr(d_second_end), _ptr(d_second_trans), B, S, Cn,
+                                           _stream()),
+          "icka_crf_expect_grad")
+
+
 # ------------------------------------------------------------------------------------------------- chunk metrics
 CHUNK_EVAL_MAX_S, CHUNK_EVAL_MAX_IDS, CHUNK_EVAL_MAX_TYPES, CHUNK_EVAL_HEAD = 512, 64, 32, 6
 

@@ -690,6 +690,53 @@ int icka_crf_constrained_decode(const float* emissions, int64_t ld, const int64_
                                 const float* start, const float* end, const float* trans, int32_t* lens, int32_t* tags_flat,
                                 int64_t capacity, float* scores, int32_t* infeasible, int32_t B, int32_t S, int32_t C,
                                 void* stream);
+/* CRF expectations (csrc/crf_expect.hip): log Z and the expectation of a path-additive payoff under the CRF distribution,
+ * with gradients.  Sequence entropy, the KL divergence between two CRFs over one sentence and an expected cost reduce to it.
+ * One launch per entry, one wave per sample, no host sync.  The chain is icka_crf_posterior's: per sample the ON-POSITIONS are
+ * position 0 and every t >= 1 with mask[b,t] != 0 (mask NULL = all on), i = 0 .. L-1.
+ * A LATTICE is (e [B,S,C] with a row stride, start [C], end [C], trans [C,C]); x_i is its e row at on-position i, its path
+ * score
+ *   s(y) = start[y_0] + sum_i x_i[y_i] + sum_{i >= 1} trans[y_{i-1}, y_i] + end[y_{L-1}],
+ * and p(y) = exp(s_p(y) - log Z_p) for the first lattice (emissions, start, end, trans).  The PAYOFF r(y) comes from a SECOND
+ * lattice (second, second_start, second_end, second_trans): every one of its four parts is nullable, a NULL part is zeros.
+ *   relative == 0 (given):    r = s_second
+ *   relative == 1 (relative): r = s_p - s_second, formed operand by operand as the values are loaded (never as the difference
+ *                             of two accumulated sums)
+ * icka_crf_expect:  log_z[b] = log Z_p and expect[b] = E_p[r(y)], f32 [B].  expect may be NULL: then only log_z is computed.
+ *   H(p) = log_z - expect (relative, no second lattice);  KL(p || q) = expect - log_z_p + log_z_q (relative, q the second
+ *   lattice, log_z_q from one more call on q with expect NULL);  an expected cost is expect in given mode with
+ *   second[b,t,j] = cost[tags[b,t], j] and the three other parts NULL.
+ * icka_crf_expect_grad:  upstream g_logz, g_expect f32 [B], each nullable (NULL = zeros).  With mu_i(j) and xi_i(k,j) the token
+ *   and pair marginals of p, for the first lattice's features f (emission cells, start at i = 0, end at i = L-1, transition
+ *   cells summed over i >= 1)
+ *     g_logz E_p[f] + g_expect (Cov_p(f, r) + [relative] E_p[f]),
+ *   and for the second lattice's features g_expect (+- E_p[f]): + given, - relative.  The contract of icka_crf_grad:
+ *   d_emissions and d_second [B,S,C] (row strides ldd, ldd2) are WRITTEN, every row of the sample, exact +0.0 in all C columns of
+ *   an off-position (pad columns are not touched); the three parameter gradients of each lattice are ACCUMULATED (+=) with
+ *   atomics over the samples.  Each of the eight outputs is nullable: NULL = not wanted.  The covariance is computed only
+ *   when g_expect and at least one of the first lattice's four outputs are given (a detached first lattice costs one plain
+ *   forward-backward).
+ *   Cov_p(1[y_i = j], r) = mu_i(j) (a_i(j) + b_i(j) - E_p[r]) with a_i(j) the expected payoff of the prefix through node i given
+ *   y_i = j and b_i(j) that of the suffix after it (expectation semiring); the transition cells use xi_i(k,j) (a_{i-1}(k) +
+ *   r_trans(k,j) + r_i(j) + b_i(j) - E_p[r]).  a + b and E_p[r] are both of size L |r|, so the kernel carries a and b minus a
+ *   wave-uniform offset per position and subtracts the mu- (xi-) weighted mean instead, which is exact: nothing of that size
+ *   is ever subtracted in f32.
+ * Limits (else ICKA_E_SHAPE, nothing launched, nothing written): C <= 64 and S*C <= 4096 (alpha and the centred a of every
+ * on-position in LDS); any B >= 1.  relative outside {0, 1}, a missing first-lattice operand or a row stride below C:
+ * ICKA_E_ARG.  Log-domain f32 recursions: for C <= 16 with the scores on the lanes and the tables in registers, otherwise
+ * through LDS (the same arithmetic in another summation order).  Scores are assumed finite: -inf is NOT supported (forbid a transition with -1e4,
+ * which gives finite results: its probabilities underflow to exact zeros).
+ * Not covered: constraints (allowed sets), packed batches. */
+int icka_crf_expect(const float* emissions, int64_t ld, const int64_t* mask, const float* start, const float* end,
+                    const float* trans, const float* second, int64_t ld2, const float* second_start,
+                    const float* second_end, const float* second_trans, int32_t relative, float* log_z, float* expect,
+                    int32_t B, int32_t S, int32_t C, void* stream);
+int icka_crf_expect_grad(const float* emissions, int64_t ld, const int64_t* mask, const float* start, const float* end,
+                         const float* trans, const float* second, int64_t ld2, const float* second_start,
+                         const float* second_end, const float* second_trans, int32_t relative, const float* g_logz,
+                         const float* g_expect, float* d_emissions, int64_t ldd, float* d_start, float* d_end,
+                         float* d_trans, float* d_second, int64_t ldd2, float* d_second_start, float* d_second_end,
+                         float* d_second_trans, int32_t B, int32_t S, int32_t C, void* stream);
 /* ---------------------------------------------------------------------------------------------------------------
  * Chunk-level scoring of a dev / test batch (csrc/metrics.hip): the counts behind the reference's accuracy / precision /
  * recall / F1, overall and per entity type -- the per-token loop of My_cross_attention.py:882-903 followed by
