@@ -1,6 +1,6 @@
-// Shared by attention.hip and gemm.hip: the LDS tile image of a head's Q / K / V rows, the MFMA fragment reads, the argument
+// Shared by attention.hip and gemm_w3.inc (compiled into gemm.hip): the LDS tile image of a head's Q / K / V rows, the MFMA fragment reads, the argument
 // block of the attention launches, and the WHOLE-HEAD forward (every score of the head in registers) as a device function --
-// the body of attn_fwd_small_kernel, which gemm_qkv_attn_kernel (gemm.hip) runs in the epilogue of the QKV projection on tiles
+// the body of attn_fwd_small_kernel, which gemm_qkv_attn_kernel (gemm_w3.inc) runs in the epilogue of the QKV projection on tiles
 // that never left the LDS.  One definition, so that the two launches and the fused one are the same arithmetic bit for bit.
 #pragma once
 #include <math.h>

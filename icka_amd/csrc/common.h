@@ -221,7 +221,7 @@ __device__ __forceinline__ float dgelu_f(float x) {
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
 
 // Chan et al.'s pairwise merge of (count, mean, M2) partial statistics: (n, mean, m2) <- (n, mean, m2) + (nb, mb, m2b).
-// Train-mode BatchNorm (gemm.hip bn_stats_tile, conv.hip bn_finalize_kernel): stable where E[x^2] - E[x]^2 cancels.
+// Train-mode BatchNorm (gemm_ws.inc bn_stats_tile, conv.hip bn_finalize_kernel): stable where E[x^2] - E[x]^2 cancels.
 __device__ __forceinline__ void bn_chan_merge(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
     if (nb == 0.f) return;
     const float nn = n + nb, d = mb - mean, f = nb / nn;

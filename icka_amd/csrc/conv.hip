@@ -9,7 +9,7 @@
 //   features_out : last NHWC map -> att f32 [B,C,7,7] (F.adaptive_avg_pool2d(x,[7,7]) of a 7x7 map = identity),
 //                  fc = mean over the 49 positions, and the region-token matrix bf16 [B*49, C] the MNER trunk reads.
 // Train-mode BatchNorm (ResNet.train_batchnorm) replaces the fold by three steps per BatchNorm: the convolution GEMM writes
-// the raw output and per-tile partial statistics (gemm.hip, icka_gemm_bn_stats / icka_conv3x3_gemm_stats), then
+// the raw output and per-tile partial statistics (gemm_fused.inc, icka_gemm_bn_stats / icka_conv3x3_gemm_stats), then
 //   bn_finalize  : partials -> batch mean / variance -> scale, shift + the running-statistics update, on the device
 //   bn_apply     : relu(raw * scale + shift [+ residual]), the residual optionally through the downsample's scale / shift
 // Rows past the last valid row of a padded (multiple-of-128) GEMM operand are written as zeros.

@@ -4,7 +4,7 @@
 // the GPU so that the exchange costs the compute stream as little as possible:
 //
 //   * wire format.  Gradients travel as bf16.  The weight-gradient GEMMs write the bf16 copy of every matrix gradient into the
-//     wire buffer from their own epilogue (icka_gemm_desc.C3, gemm.hip), so only what no GEMM produces -- bias / LayerNorm
+//     wire buffer from their own epilogue (icka_gemm_desc.C3, gemm_core.h), so only what no GEMM produces -- bias / LayerNorm
 //     vectors, the classifier, the embedding tables -- still has to be cast: icka_dp_cast_chunks does that for one bucket in
 //     ONE launch over a chunk table (scattered ranges of the flat gradient buffer), and icka_dp_cast_back_scaled brings the
 //     reduced bucket back to f32 with the 1/world factor folded in (the all-reduce is then a plain SUM).

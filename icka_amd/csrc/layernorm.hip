@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a_) {
     a.drop = drop_resolve(a.drop);
     const int lane = threadIdx.x & 63;
     const int wid = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
-    ln_fwd_rows<NCH>(a, wid, nw, a.M, lane);      // (ln_row.h: the row body shared with gemm.hip's gemm_ln_kernel)
+    ln_fwd_rows<NCH>(a, wid, nw, a.M, lane);      // (ln_row.h: the row body shared with gemm_fused.inc's gemm_ln_kernel)
 }
 
 struct LnBwdArgs {

@@ -1,6 +1,6 @@
 // ln_row.h -- the forward row body of the fused bias + dropout + residual + LayerNorm (BertSelfOutput.forward
 // Cross_Modal_Interaction_Module.py:561-565, BertOutput.forward :532-536, BertLayerNorm.forward :518-522), shared by the
-// stand-alone row kernel (layernorm.hip: ln_fwd_kernel) and by the GEMM kernel that finishes its own rows (gemm.hip:
+// stand-alone row kernel (layernorm.hip: ln_fwd_kernel) and by the GEMM kernel that finishes its own rows (gemm_fused.inc:
 // gemm_ln_kernel): ONE definition of the arithmetic, so the two paths give bitwise the same y / twin / xhat / rstd.
 #pragma once
 #include "common.h"

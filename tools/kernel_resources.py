@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic: per-kernel register / scratch / occupancy table of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/kernel_resources.py icka_amd/csrc/gemm.hip [name-filter]"""
+usage: python tools/kernel_resources.py icka_amd/csrc/gemm.hip [name-filter]   (gemm.hip = the whole GEMM family: it includes gemm_core.h and the gemm_*.inc fragments)"""
 import re
 import subprocess
 import sys

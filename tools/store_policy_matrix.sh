@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-site store-policy matrix: the c2 step with ordinary instead of streaming stores for the MAIN
-# output of ONE producer site at a time (ICKA_GEMM_PLAIN_MASK, gemm.hip: site_bit), same box, baseline first / middle / last;
+# output of ONE producer site at a time (ICKA_GEMM_PLAIN_MASK, csrc/gemm.hip: site_bit), same box, baseline first / middle / last;
 # then the union of the sites that beat the baseline.  usage (on the GPU box): bash tools/store_policy_matrix.sh [out.txt]
 OUT=${1:-gpurun_out/store_policy_matrix.txt}
 ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-roofline --no-optimizer-leg --no-eager-leg"

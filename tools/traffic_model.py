@@ -45,7 +45,7 @@ G = [
 
 
 def big_group_fetch():
-    """Fetch of the grouped weight-gradient launch under its own tile order (csrc/gemm.hip gemm_big_group_kernel: XCD x takes
+    """Fetch of the grouped weight-gradient launch under its own tile order (csrc/gemm_grouped.inc gemm_big_group_kernel: XCD x takes
     the contiguous run x of the problems' concatenated lists of 256 x 128 tiles, each list ordered along its shorter side):
     every XCD fetches the distinct dY (256 x M x 2 B) and X (128 x M x 2 B) panels of its run.  Returns (tile panels, the
     second read of dY by the column-sum blocks of the same launch) in bytes."""
