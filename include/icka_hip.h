@@ -864,7 +864,10 @@ int icka_conv_features_out(const void* x, float* att, float* fc, void* tokens, i
  *  2. icka_bn_finalize: merges the tiles' partials per channel in a fixed order (Chan's parallel variance), then
  *     scale = weight / sqrt(var + eps), shift = bias - mean * scale, running_mean / running_var <- (1 - m) * old + m * (mean,
  *     var * n / (n - 1)), m = momentum, or 1 / (num_batches_tracked + 1) when momentum < 0 (momentum=None).  In place on the
- *     device: graph-capturable, no host synchronisation.
+ *     device: graph-capturable, no host synchronisation.  num_batches_tracked is only read.  A partial whose count is 0 is
+ *     skipped whatever its mean and M2 hold.  With a total count n == 1 the variance is 0 and so is the value blended into
+ *     running_var (no n / (n - 1)); with n == 0 (every count zero) the mean is 0 too: scale = weight / sqrt(eps), shift = bias,
+ *     and both running statistics become (1 - m) * old.  (The Python caller refuses rows_valid < 2.)
  *  3. icka_bn_apply: y = [relu](raw * scale + shift [+ r]) on rows < rows_valid, zeros on [rows_valid, rows_padded); r =
  *     residual (bf16), or residual * res_scale + res_shift when res_scale is given (the downsample branch); y may be raw.
  *     Adds 1 to *nbt_a and *nbt_b (int64 num_batches_tracked, each nullable): the increment of the BatchNorms it applies. */

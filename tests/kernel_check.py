@@ -77,6 +77,18 @@ is the eps_fmt |ref| term of the bound; f32 outputs show how much room the accum
                     adamw_dev bitwise adamw
       dp casts      cast_chunks and cast_back_scaled bitwise (a NaN becomes 0x7fc0); copy_many, zero_f32 bitwise;
                     scalar_ratio 0.080, loss_accumulate exact
+    convolution and train-mode BatchNorm (tests/conv_check.py), worst over the cases of each kernel
+      conv3x3_gemm        y 0.973 (C 64 / 128, Cout 64 .. 192, both strides, maps from 1 x 1, all four epilogues, bias and null,
+                          aux at ld Cout and Cout + 8; padded rows and whole padded tiles bitwise the epilogue of bias (+ aux))
+      gemm_bn_stats       raw 0.996; partials: mean 0.008, M2 0.003, accumulators of a large mean: mean 0.023, M2 0.003 (the
+                          worst-case accumulator error E carries these bounds); integer accumulators (E = 0: the slice sums and
+                          merges alone): mean 0.014, M2 0.071; counts exact, tiles without a valid row (0, 0, 0)
+      conv3x3_gemm_stats  raw 0.937 and bitwise the bias-less EPI_NONE convolution; mean < 0.001, M2 0.001
+      bn_finalize         scale 0.220, shift 0.201, running_mean 0.246, running_var 0.238 (every momentum form, old statistics
+                          random); tile means of 100: 0.101 / 0.055 / 0.065 / 0.128; n == 1: 0.175 / 0.174 / 0.231 / 0.158;
+                          n == 0: 0.175 / 0 / 0.165 / 0.158; num_batches_tracked unchanged
+      chain               stats GEMM -> finalize -> apply against F.batch_norm + ReLU: y 0.950 (scale / shift 0.001,
+                          running_mean 0.008, running_var 0.028 of their propagated bounds)
 
 No guard band was disturbed and no NaN pad reached a result in any case.  Two terms of the bounds go beyond the plain
 roundoff sums, both named in the docstrings below: the GELU allowance is RELATIVE (1e-4 |gelu|) for z >= 1, as
