@@ -10,7 +10,7 @@ from .modeling import (BertAttention, BertCoAttention, BertCrossAttention, BertC
                        BertSelfOutput, MTCCMBertForMMTokenClassificationCRF, cls_layer_both, scalar_gate_fusion,
                        resolved_precision, set_precision, token_ce_loss)
 from .arena import ParamArena
-from .crf import CRF, ConstrainedPaths, NBestPaths
+from .crf import CRF, ConstrainedPaths, NBestPaths, SampledPaths, minimum_risk
 from .lstm import BiLSTM
 from .modeling import MTCCMBertForMMTokenClassificationCRF_gate_1
 from .dp import GradReducer
@@ -33,4 +33,4 @@ __all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "Bert
            "token_ce_loss", "set_precision", "resolved_precision", "ParamArena", "cross_modal", "PromptRobertaModel",
            "GradReducer", "graph", "DevicePrefetcher", "GraphedModule", "GraphedStep", "TrainStep", "packing", "set_packed",
            "PackOverflowError", "TokenBudgetBatchSampler", "metrics", "ChunkEvaluator", "EntityDecoder", "attention_maps",
-           "NBestPaths", "NBestEntities", "ConstrainedPaths"]
+           "NBestPaths", "NBestEntities", "ConstrainedPaths", "SampledPaths", "minimum_risk"]

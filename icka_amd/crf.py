@@ -354,6 +354,79 @@ class CRF(ArenaModule):
                     out.lens, out.n_paths, out.scores, out.tags)
         return out
 
+    def sample(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None, num_samples: int = 1,
+               seed=0) -> "SampledPaths":
+        """``num_samples`` independent exact draws from ``p(y | emissions)`` per sample (``icka_crf_sample``; the algorithm and
+        the uniforms are written out in include/icka_hip.h): one launch, no host sync, capturable in a graph.  A path has one
+        tag per on-position (position 0 and the positions with ``mask != 0``).  ``seed``: an int in [0, 2^64), or a device
+        int64 [1] tensor whose two 32-bit halves are XORed into a by-value seed of 0 -- a captured graph that increments that
+        tensor draws fresh paths on every replay.  Equal arguments give bitwise equal results; no process-wide state is
+        read.  A tag whose step weight underflows to 0 (a ``-1e4`` transition) is never drawn.  Detached.  Limits:
+        ``num_tags <= 64``, ``1 <= num_samples <= 64``, ``S * num_tags <= 12288``, ``B <= 2048``.  Sampling under allowed sets
+        and packed batches are not covered."""
+        e, _, m = self._prep(emissions.detach(), None, mask)
+        self._arena()
+        B, S, Cn = e.shape
+        if isinstance(num_samples, bool) or not isinstance(num_samples, int):
+            raise ValueError("CRF.sample: num_samples must be an int, got %s" % type(num_samples).__name__)
+        if not 1 <= num_samples <= K.CRF_SAMPLE_MAX_K:     # before the buffers are sized by it
+            raise ValueError("CRF.sample: 1 <= num_samples <= %d, got %d" % (K.CRF_SAMPLE_MAX_K, num_samples))
+        if S * Cn > K.CRF_MAX_SC:
+            raise ValueError("CRF.sample: S * num_tags <= %d, got %d * %d = %d" % (K.CRF_MAX_SC, S, Cn, S * Cn))
+        if B > K.CRF_FLAT_MAX_B:
+            raise ValueError("CRF.sample: B <= %d, got %d" % (K.CRF_FLAT_MAX_B, B))
+        seed_dev = None
+        if isinstance(seed, torch.Tensor):
+            if seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != e.device:
+                raise ValueError("CRF.sample: a tensor seed must be int64 [1] on %s, got %s %s on %s"
+                                 % (e.device, seed.dtype, tuple(seed.shape), seed.device))
+            seed_dev, seed = seed.reshape(1), 0
+        elif isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError("CRF.sample: seed must be an int in [0, 2^64) or a device int64 [1] tensor, got %r" % (seed,))
+        out = SampledPaths(B, S, num_samples, e.device)
+        K.crf_sample(e, m, self.start_transitions.detach(), self.end_transitions.detach(), self.transitions.detach(),
+                     num_samples, seed, seed_dev, out.lens, out.log_z, out.scores, out.tags)
+        return out
+
+    def path_llh(self, emissions: torch.Tensor, paths, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``log p(path | emissions)`` of every row of ``paths`` -- a ``DeviceTags`` (one row), an ``NBestPaths`` or a
+        ``SampledPaths`` -- f32 [B, R], differentiable in ``emissions`` and the three parameters: the candidate
+        log-probabilities of minimum-risk training (``minimum_risk``).  Each row becomes singleton allowed sets at the
+        on-positions (torch ops on the device, no host sync) and goes through ``constrained_llh``'s kernels, one call per
+        row: ``score(path) - log Z`` in the chain over position 0 and the positions with ``mask != 0``.  A missing rank (-1
+        tags), a tag outside [0, num_tags) or a path shorter than its sample's chain is an empty set: value ``-inf``, zero
+        gradient."""
+        who = "CRF.path_llh"
+        if isinstance(paths, DeviceTags):
+            lens, rows = paths.lens, paths.tags_flat[None, :]
+        elif isinstance(paths, (NBestPaths, SampledPaths)):
+            lens, rows = paths.lens, paths.tags
+        else:
+            raise ValueError("%s: paths must be a DeviceTags, NBestPaths or SampledPaths, got %s" % (who, type(paths).__name__))
+        e, _, m = self._prep(emissions, None, mask)
+        B, S, Cn = e.shape
+        if lens.numel() != B or lens.device != e.device:
+            raise ValueError("%s: paths hold %d samples on %s for a batch of %d on %s"
+                             % (who, lens.numel(), lens.device, B, e.device))
+        if S * Cn > K.CRF_MAX_SC:
+            raise ValueError("%s: S * num_tags <= %d, got %d * %d = %d" % (who, K.CRF_MAX_SC, S, Cn, S * Cn))
+        if m is not None:
+            m[:, 0] = 1            # (m is _prep's own copy) position 0 is on, as in posterior
+        on = torch.ones(B, S, dtype=torch.bool, device=e.device) if m is None else m != 0
+        ln = lens.to(torch.int64)
+        rank = on.to(torch.int64).cumsum(1) - 1                         # index of an on-position in its sample's path
+        cap = rows.shape[1]
+        idx = ((ln.cumsum(0) - ln)[:, None] + rank).clamp(0, cap - 1)
+        inside = on & (rank < ln[:, None])
+        A = self._arena()
+        out = []
+        for r in range(rows.shape[0]):
+            t = rows[r].to(torch.int64)[idx]
+            ok = inside & (t >= 0) & (t < Cn)
+            al = torch.where(ok, torch.ones_like(t) << t.clamp(0, 63), torch.zeros_like(t)).contiguous()
+            out.append(_CrfConstrainedFn.apply(A.anchor, e, al, m, self, A))
+        return torch.stack(out, 1)
+
     # ------------------------------------------------------------------------------------------------- posteriors
     def marginals(self, emissions: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``P(y_t = j | emissions)``, f32 in the layout of ``emissions`` ([B,S,C], or [S,B,C] without ``batch_first``): the
@@ -819,3 +892,68 @@ class NBestPaths(_JointBuffer):
     def __repr__(self) -> str:
         return "NBestPaths(batch=%d, nbest=%d, capacity=%d, device=%s)" % (
             self.batch_size, self.nbest, self.capacity, self.joint.device)
+
+
+class SampledPaths(_JointBuffer):
+    """The outputs of ``CRF.sample`` on the device, in ONE buffer (``joint``, int32 words; ``log_z`` and ``scores`` are f32 views
+    of it) so that ``host()`` is one device-to-host copy:
+
+        lens int32 [B] | log_z f32 [B] | scores f32 [B, num_samples] | tags int32 [num_samples, B*S]
+
+    ``lens[b]`` is the length of every draw of sample b, ``scores[b, k]`` the score of draw k and row k of ``tags`` holds draw k
+    of all samples back to back, sample b at ``sum(lens[:b])``: ``draw(k)`` is a ``DeviceTags`` view of it."""
+
+    def __init__(self, B: int, S: int, num_samples: int, device):
+        cap = B * S
+        super().__init__([("lens", B), ("log_z", B), ("scores", B * num_samples), ("tags", num_samples * cap)], device)
+        part = self.part
+        self.batch_size, self.capacity, self.num_samples = B, cap, num_samples
+        self.lens = part("lens")
+        self.log_z = part("log_z").view(F32)
+        self.scores = part("scores").view(F32).view(B, num_samples)
+        self.tags = part("tags").view(num_samples, cap)
+
+    def draw(self, k: int) -> DeviceTags:
+        """Draw ``k`` of every sample as a ``DeviceTags`` (a view: no copy), which ``CRF.posterior(paths=...)``,
+        ``CRF.path_llh`` and ``metrics.ChunkEvaluator`` take as it is."""
+        if not 0 <= k < self.num_samples:
+            raise IndexError("draw %d of %d" % (k, self.num_samples))
+        return DeviceTags(self.lens, self.tags[k])
+
+    def log_probs(self) -> torch.Tensor:
+        """``scores - log_z[:, None]`` on the device, f32 [B, num_samples]: the log-probability of every draw."""
+        return self.scores - self.log_z[:, None]
+
+    def unpack(self, h: torch.Tensor) -> dict:
+        """What ``host()`` returns, from a host copy ``h`` of ``joint`` (the caller's own, as part of a larger copy):
+        python lists keyed by field name, ``scores`` and ``tags`` nested by row."""
+        return {"lens": self.part("lens", h).tolist(), "log_z": self.part("log_z", h).view(F32).tolist(),
+                "scores": self.part("scores", h).view(F32).view(self.batch_size, self.num_samples).tolist(),
+                "tags": self.part("tags", h).view(self.num_samples, self.capacity).tolist()}
+
+    def tolist(self) -> List[List[tuple]]:
+        """Per sample a list of ``num_samples`` pairs ``(path, log_prob)`` in draw order (one device-to-host copy)."""
+        h = self.host()
+        out, o = [], 0
+        for b, n in enumerate(h["lens"]):
+            out.append([(h["tags"][k][o:o + n], h["scores"][b][k] - h["log_z"][b]) for k in range(self.num_samples)])
+            o += n
+        return out
+
+    def __repr__(self) -> str:
+        return "SampledPaths(batch=%d, num_samples=%d, capacity=%d, device=%s)" % (
+            self.batch_size, self.num_samples, self.capacity, self.joint.device)
+
+
+def minimum_risk(logp: torch.Tensor, cost: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """The risk of a candidate set, f32 [B]: ``sum_r q_r cost_r`` with ``q = softmax_r(scale * logp)`` over the rows with
+    finite ``logp`` ([B, R]: ``CRF.path_llh``; ``cost`` [B, R]: ``metrics.f1_cost``).  A row with a non-finite ``logp`` (a
+    missing rank) has no weight and passes no gradient; a sample with no finite row returns 0.  Plain torch."""
+    if logp.dim() != 2 or tuple(cost.shape) != tuple(logp.shape):
+        raise ValueError("minimum_risk: logp and cost must both be [B, R], got %s and %s" % (tuple(logp.shape), tuple(cost.shape)))
+    finite = torch.isfinite(logp)
+    some = finite.any(1, keepdim=True)
+    z = torch.where(finite, logp * scale, torch.full_like(logp, float("-inf")))
+    z = torch.where(some, z, torch.zeros_like(z))               # (a softmax over nothing but -inf would be NaN)
+    q = torch.where(finite, torch.softmax(z, 1), torch.zeros_like(z))
+    return (q * torch.where(finite, cost.to(logp.dtype), torch.zeros_like(logp))).sum(1)

@@ -1,5 +1,5 @@
-// What the CRF kernels (crf.hip, crf_posterior.hip, crf_nbest.hip, crf_constrained.hip, crf_expect.hip) and the chunk pass of metrics.hip
-// share: the limits of the entries, the label-table word bits with the chunk rule, the walk over a sample's on-positions and
+// What the CRF kernels (crf.hip, crf_posterior.hip, crf_nbest.hip, crf_constrained.hip, crf_expect.hip, crf_sample.hip) and the chunk
+// passes of metrics.hip and chunk_counts.hip share: the limits of the entries, the label-table word bits with the chunk rule, the walk over a sample's on-positions and
 // the 16-lane wave primitives of the register / shuffle forms.  One definition each; everything is constexpr or forced inline.
 #pragma once
 #include "common.h"

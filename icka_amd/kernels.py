@@ -1165,6 +1165,47 @@ def crf_nbest(emissions, mask, start, end, trans, nbest, lens, n_paths, scores, 
           "icka_crf_nbest")
 
 
+CRF_SAMPLE_MAX_K = 64
+
+
+def crf_sample(emissions, mask, start, end, trans, num_samples, seed, seed_dev, lens, log_z, scores, tags_flat):
+    """``num_samples`` exact draws from the CRF distribution of every sample (icka_crf_sample, include/icka_hip.h): ``lens``
+    int32 [B], ``log_z`` f32 [B], ``scores`` f32 [B, num_samples], ``tags_flat`` int32 [num_samples, capacity >= B*S] (row k:
+    draw k in the layout of ``crf_nbest``).  ``seed``: an int in [0, 2^64); ``seed_dev``: None or a device int64 [1] / int32 [2]
+    tensor whose two 32-bit words are XORed into the halves of the seed.  One launch, no host sync.  Every operand is checked
+    on the host (ValueError, then TypeError for the device) before anything is launched."""
+    ops = _CrfOperands("crf_sample", emissions, start, end, trans)
+    B, S, Cn = ops.shape
+    if isinstance(num_samples, bool) or not isinstance(num_samples, int):
+        raise ValueError("crf_sample: num_samples must be an int, got %s" % type(num_samples).__name__)
+    if not 1 <= num_samples <= CRF_SAMPLE_MAX_K:
+        raise ValueError("crf_sample: 1 <= num_samples <= %d, got %d" % (CRF_SAMPLE_MAX_K, num_samples))
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError("crf_sample: seed must be an int in [0, 2^64), got %r" % (seed,))
+    if B < 1 or S < 1 or not 1 <= Cn <= 64 or S * Cn > CRF_MAX_SC or B > CRF_FLAT_MAX_B:
+        raise ValueError("crf_sample: 1 <= B <= %d, 1 <= num_tags <= 64 and S * num_tags <= %d, got [%d, %d, %d]"
+                         % (CRF_FLAT_MAX_B, CRF_MAX_SC, B, S, Cn))
+    ops.vec(lens, "lens", torch.int32, (B,))
+    ops.vec(log_z, "log_z", F32, (B,))
+    ops.vec(scores, "scores", F32, (B, num_samples))
+    ops.opt(mask, "mask", torch.int64, (B, S))
+    ops.vec(tags_flat, "tags_flat", torch.int32,
+            fits=lambda t: t.dim() == 2 and t.shape[0] == num_samples and t.shape[1] >= B * S,
+            what="a contiguous int32 tensor of shape (%d, >= %d)" % (num_samples, B * S))
+    if seed_dev is not None:
+        ok = isinstance(seed_dev, torch.Tensor) and seed_dev.is_contiguous() and (
+            (seed_dev.dtype == torch.int64 and seed_dev.numel() == 1) or (seed_dev.dtype == torch.int32 and seed_dev.numel() == 2))
+        if not ok:
+            raise ValueError("crf_sample: seed_dev must be a contiguous int64 [1] or int32 [2] tensor, got %s %s"
+                             % (getattr(seed_dev, "dtype", type(seed_dev).__name__), tuple(getattr(seed_dev, "shape", ()))))
+        ops.used.append(seed_dev)
+    ops.same_device()
+    check(_lib.load().icka_crf_sample(emissions.data_ptr(), Cn, _ptr(mask), start.data_ptr(), end.data_ptr(),
+                                      trans.data_ptr(), num_samples, seed, _ptr(seed_dev), lens.data_ptr(), log_z.data_ptr(),
+                                      scores.data_ptr(), tags_flat.data_ptr(), tags_flat.shape[1], B, S, Cn, _stream()),
+          "icka_crf_sample")
+
+
 def _crf_constrained_operands(who, emissions, mask, allowed, start, end, trans, flat_b=False):
     """What the three constrained-CRF entries check before their own operands: the limits, ``allowed`` and ``mask``."""
     ops = _CrfOperands(who, emissions, start, end, trans)
@@ -1350,6 +1391,44 @@ def chunk_eval(labels, output_mask, label_table, counters, ntypes, *, lens=None,
     check(_lib.load().icka_chunk_eval(_ptr(lens), _ptr(tags_flat), cap, _ptr(pred), _ld(pred), labels.data_ptr(),
                                       output_mask.data_ptr(), label_table.data_ptr(), counters.data_ptr(), B, S, L,
                                       int(ntypes), _stream()), "icka_chunk_eval")
+
+
+CHUNK_COUNTS_MAX_R = 64
+
+
+def chunk_counts(lens, tags, labels, output_mask, label_table, counts, ntypes):
+    """Write the chunk counts of every (path row, sample) into ``counts`` int32 [R, B, 4] = (correct_preds, total_preds,
+    total_correct, bad) (icka_chunk_counts, include/icka_hip.h): ``lens`` int32 [B], ``tags`` int32 [R, capacity] with unit
+    column stride (the rows of ``crf_nbest`` / ``crf_sample``, or one ``tags_flat`` as [1, capacity]).  One launch, no host
+    sync."""
+    _dev(labels, "labels")
+    if labels.dim() != 2:
+        raise ValueError("labels must be [B, S], got %s" % (tuple(labels.shape),))
+    B, S = labels.shape
+    _i64(labels, "labels", (B, S)); _i64(output_mask, "output_mask", (B, S))
+    if not 1 <= S <= CHUNK_EVAL_MAX_S or not 1 <= B <= CRF_FLAT_MAX_B:
+        raise ValueError("chunk_counts: 1 <= B <= %d and 1 <= S <= %d, got [%d, %d]" % (CRF_FLAT_MAX_B, CHUNK_EVAL_MAX_S, B, S))
+    _dev(label_table, "label_table"); _dev(counts, "counts"); _dev(lens, "lens"); _dev(tags, "tags")
+    L = label_table.numel()
+    if label_table.dtype != torch.int32 or label_table.dim() != 1 or not label_table.is_contiguous() \
+            or not 1 <= L <= CHUNK_EVAL_MAX_IDS:
+        raise ValueError("label_table must be a contiguous int32 vector of 1 .. %d words" % CHUNK_EVAL_MAX_IDS)
+    if not 1 <= ntypes <= CHUNK_EVAL_MAX_TYPES:
+        raise ValueError("chunk_counts: 1 <= ntypes <= %d, got %d" % (CHUNK_EVAL_MAX_TYPES, ntypes))
+    if lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous():
+        raise ValueError("lens must be a contiguous int32 tensor of shape (%d,), got %s %s" % (B, lens.dtype, tuple(lens.shape)))
+    if tags.dtype != torch.int32 or tags.dim() != 2 or not 1 <= tags.shape[0] <= CHUNK_COUNTS_MAX_R \
+            or (tags.shape[1] > 1 and tags.stride(1) != 1) or (tags.shape[0] > 1 and tags.stride(0) < tags.shape[1]):
+        raise ValueError("tags must be int32 [1 .. %d, capacity] with unit column stride, got %s %s"
+                         % (CHUNK_COUNTS_MAX_R, tags.dtype, tuple(tags.shape)))
+    R, cap = tags.shape
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (R, B, 4) or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int32 tensor of shape %s, got %s %s"
+                         % ((R, B, 4), counts.dtype, tuple(counts.shape)))
+    check(_lib.load().icka_chunk_counts(lens.data_ptr(), tags.data_ptr(), cap, tags.stride(0) if R > 1 else cap, R,
+                                        labels.data_ptr(), output_mask.data_ptr(), label_table.data_ptr(), counts.data_ptr(),
+                                        B, S, L, int(ntypes), _stream()), "icka_chunk_counts")
+    return counts
 
 
 def loss_accumulate(loss, acc):

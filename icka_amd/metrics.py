@@ -177,6 +177,19 @@ def evaluate_lists(pred: Sequence[Sequence[int]], gold: Sequence[Sequence[int]],
     return _scores_from_table(table, types, default.split("-")[-1])
 
 
+def f1_cost(counts: torch.Tensor) -> torch.Tensor:
+    """``1 - F1`` of every candidate path, f32 [B, R], from ``ChunkEvaluator.path_counts``'s int32 [R, B, 4]:
+    ``1 - 2 c / (p + g)`` with c = correct_preds, p = total_preds, g = total_correct; 0 where ``p + g == 0`` (nothing to find,
+    nothing predicted), 1 for a bad sample.  Plain torch on the tensor's own device, no host sync."""
+    if not isinstance(counts, torch.Tensor) or counts.dim() != 3 or counts.shape[2] != 4 or counts.is_floating_point():
+        raise ValueError("f1_cost: counts must be an integer [R, B, 4] tensor, got %s %s"
+                         % (getattr(counts, "dtype", type(counts).__name__), tuple(getattr(counts, "shape", ()))))
+    c, p, g, bad = (counts[..., i].to(torch.float32) for i in range(4))
+    n = p + g
+    cost = torch.where(n > 0, 1.0 - 2.0 * c / n.clamp(min=1.0), torch.zeros_like(n))
+    return torch.where(bad != 0, torch.ones_like(cost), cost).transpose(0, 1).contiguous()
+
+
 class ChunkEvaluator(object):
     """Accumulates the chunk-level counts of a dev / test epoch on the device.
 
@@ -246,6 +259,25 @@ class ChunkEvaluator(object):
             rows = [(list(r)[:S] + [-1] * S)[:S] for r in pred]
             kw = {"pred": torch.tensor(rows, dtype=torch.int64).reshape(B, S).to(self.device)}
         K.chunk_eval(labels, output_mask, self._table, self.counters, len(self.types), **kw)
+
+    def path_counts(self, paths, labels, output_mask) -> torch.Tensor:
+        """The chunk counts of every candidate path of every sample, int32 [R, B, 4] = (correct_preds, total_preds,
+        total_correct, bad) on the device (``icka_chunk_counts``): ``paths`` a ``crf.DeviceTags`` (R = 1), ``crf.NBestPaths``
+        or ``crf.SampledPaths`` (one row per rank / draw).  The rules are ``update``'s; nothing is added to ``counters``.  A
+        sample ``update`` would count as ``bad_ids`` -- a rank an N-best sample does not have (-1 tags) among them -- gets
+        (0, 0, 0, 1).  One launch, no host sync; ``f1_cost`` turns the result into a per-candidate cost."""
+        from .crf import DeviceTags, NBestPaths, SampledPaths
+        self._ensure(labels.device if isinstance(labels, torch.Tensor) and labels.is_cuda else None)
+        labels = self._i64(labels, "labels")
+        output_mask = self._i64(output_mask, "output_mask")
+        if isinstance(paths, DeviceTags):
+            lens, rows = paths.lens, paths.tags_flat[None, :]
+        elif isinstance(paths, (NBestPaths, SampledPaths)):
+            lens, rows = paths.lens, paths.tags
+        else:
+            raise ValueError("path_counts: paths must be a DeviceTags, NBestPaths or SampledPaths, got %s" % type(paths).__name__)
+        counts = torch.empty(rows.shape[0], labels.shape[0], 4, dtype=torch.int32, device=self.device)
+        return K.chunk_counts(lens, rows, labels, output_mask, self._table, counts, len(self.types))
 
     def add_loss(self, loss: torch.Tensor) -> None:
         """``dev_total_loss += loss.item(); index += 1`` (My_cross_attention.py:877-878) on the device, in float64: the f32

@@ -644,6 +644,47 @@ int icka_crf_posterior(const float* emissions, int64_t ld, const int64_t* mask, 
 int icka_crf_nbest(const float* emissions, int64_t ld, const int64_t* mask, const float* start, const float* end,
                    const float* trans, int32_t nbest, int32_t* lens, int32_t* n_paths, float* scores, int32_t* tags_flat,
                    int64_t capacity, int32_t B, int32_t S, int32_t C, void* stream);
+/* Sampling (csrc/crf_sample.hip): num_samples = K independent EXACT draws from p(y | x) = exp(score(y) - log Z) of every
+ * sample, by forward filtering and backward sampling.  One launch, one wave per sample, no host sync, capturable.  The chain
+ * is icka_crf_posterior's: per sample the ON-POSITIONS p_0 < .. < p_{L-1} are position 0 and every t >= 1 with
+ * mask[b,t] != 0 (mask NULL = all on), L their number, x_0 .. x_{L-1} the emission rows at them, and
+ *   score(y) = start[y_0] + x_0[y_0] + sum_{i >= 1} (trans[y_{i-1}, y_i] + x_i[y_i]) + end[y_{L-1}].
+ * FORWARD PASS, f32, always in the LOG domain (for every C and S: there is no scaled linear form and no fallback here), the
+ * arithmetic of icka_crf_posterior's log-domain form RE-CENTRED at every position, because a draw needs alpha_i only up to a
+ * constant per position and centred values keep their f32 digits on long chains:
+ *   a_0 = start + x_0,  a_i(v) = (m + log sum_u exp((alpha_{i-1}(u) + trans[u,v]) - m)) + x_i[v],  m the maximum of the
+ *   exponent over u;  kappa_i = max_v a_i(v),  alpha_i = a_i - kappa_i (what stays in LDS for every on-position: the true
+ *   forward score minus kappa_0 + .. + kappa_i);
+ *   log_z[b] = (kappa_0 + .. + kappa_{L-1}, summed in this order) + (m + log sum_j exp((alpha_{L-1}(j) + end[j]) - m)).
+ * DRAW k (k = 0 .. K-1), one tag per on-position, from the last to the first:
+ *   y_{L-1} from the weights w_j = exp((alpha_{L-1}(j) + end[j]) - m); then for i = L-1 .. 1
+ *   y_{i-1} from the weights w_u = exp((alpha_{i-1}(u) + trans[u, y_i]) - m);  m = the maximum of the exponent over the tags.
+ *   One draw is an inverse CDF in TAG ORDER: cum_j = w_0 + .. + w_j summed sequentially in f32, W = cum_{C-1}; the drawn tag
+ *   is the smallest j with cum_j > r * W (the product in f32).  If rounding leaves none it is the last j with w_j > 0.  A tag
+ *   whose f32 weight is exactly 0 is therefore never drawn: a transition or start of -1e4 works as a hard constraint here too.
+ * UNIFORMS: the tag at on-position p_i of draw k of sample b uses r = (h >> 8) * 2^-24 with h = the counter hash of
+ *   common.h (icka_hash) of (s0, s1, idx), idx = (b * K + k) * S + p_i in 32-bit arithmetic, s0 / s1 the low / high half of
+ *   the by-value seed, each XORed with seed_dev[0] / seed_dev[1] when the nullable DEVICE pointer seed_dev is given.  No
+ *   process-wide state takes part (the dropout nonce is not read): equal arguments give bitwise equal outputs, and a captured
+ *   graph draws fresh paths on every replay when a node of the graph changes the caller's seed_dev words.
+ * Outputs:
+ *   lens int32 [B]           L
+ *   log_z f32 [B]
+ *   scores f32 [B, K]        score of draw k, summed in f32 from left to right as in icka_crf_nbest:
+ *                            ((start + x_0) + trans) + x_1 .. + end; scores - log_z is the draw's log-probability
+ *   tags_flat int32 [K, capacity], capacity >= B*S: row k holds draw k of all samples in the layout of icka_crf_nbest
+ *                            (sample b at sum(lens[0 .. b-1]), summed inside the kernel), so (lens, row k) goes to
+ *                            icka_crf_posterior, icka_chunk_eval and icka_chunk_counts as it is; entries past sum(lens) of
+ *                            every row are left as they are.
+ * Limits (else ICKA_E_SHAPE, nothing launched, nothing written): 1 <= C <= 64, S*C <= 12288, 1 <= K <= 64, B <= 2048.
+ * C <= 16 draws four paths per pass on the four 16-lane rows of the wave, larger C one path per pass: the same arithmetic.
+ * Emissions and parameters are assumed finite; on non-finite input the paths mean nothing, but every stored tag is in
+ * [0, C) and nothing outside the sample's own segments is touched.
+ * Not covered: sampling under allowed sets; packed batches. */
+int icka_crf_sample(const float* emissions, int64_t ld, const int64_t* mask, const float* start, const float* end,
+                    const float* trans, int32_t num_samples, uint64_t seed, const uint32_t* seed_dev, int32_t* lens,
+                    float* log_z, float* scores, int32_t* tags_flat, int64_t capacity, int32_t B, int32_t S, int32_t C,
+                    void* stream);
 /* The constrained CRF (csrc/crf_constrained.hip): every on-position carries a SET of allowed tags.  Training on partially
  * labelled data maximises the marginal likelihood of all paths inside the sets; decoding returns the best path inside them.
  * One launch per entry, one wave per sample, no host sync.  The chain is icka_crf_posterior's: per sample the ON-POSITIONS
@@ -762,6 +803,21 @@ int icka_crf_expect_grad(const float* emissions, int64_t ld, const int64_t* mask
 int icka_chunk_eval(const int32_t* lens, const int32_t* tags_flat, int64_t capacity, const int64_t* pred, int64_t ld_pred,
                     const int64_t* labels, const int64_t* output_mask, const int32_t* label_table, int64_t* counters,
                     int32_t B, int32_t S, int32_t L, int32_t ntypes, void* stream);
+/* Per-path, per-sample chunk counts (csrc/chunk_counts.hip): what turns the rows of icka_crf_nbest or icka_crf_sample into a
+ * per-candidate F1 cost.  One launch, one wave per (sample, row), no atomics, no host sync.  lens int32 [B] and tags_flat
+ * int32 [R, capacity] with row stride ld_tags >= capacity: row r holds one path per sample back to back (path b at
+ * sum(lens[0 .. b-1]), summed inside the kernel).  labels, output_mask, label_table, L and ntypes are icka_chunk_eval's.
+ *   counts int32 [R, B, 4] = (correct_preds, total_preds, total_correct, bad), WRITTEN, not accumulated.
+ * The kept positions, the skip bit, start / term and the chunks are those of icka_chunk_eval, rule for rule, applied to
+ * (lens, row r): for every r the sums over b of the first three columns are what icka_chunk_eval adds to correct_preds,
+ * total_preds, total_correct for that row, and the sum of the fourth is what it adds to bad_ids.  A bad sample -- a path
+ * shorter than n0, a segment outside [0, capacity), a gold id at j < n0 or a path id at a kept position outside [0, L),
+ * such as the -1 of a rank an N-best sample does not have -- gets (0, 0, 0, 1); no id is used as an index unchecked.
+ * Limits (else ICKA_E_SHAPE, nothing launched): 1 <= S <= 512, L <= 64, ntypes <= 32, 1 <= R <= 64, 1 <= B <= 2048.
+ * Not covered: per-type counts. */
+int icka_chunk_counts(const int32_t* lens, const int32_t* tags_flat, int64_t capacity, int64_t ld_tags, int32_t R,
+                      const int64_t* labels, const int64_t* output_mask, const int32_t* label_table, int32_t* counts,
+                      int32_t B, int32_t S, int32_t L, int32_t ntypes, void* stream);
 /* acc[0] += (double)loss[0], acc[1] += 1 (one launch, stream-ordered): the dev loop's `dev_total_loss += loss.item();
  * index += 1` (My_cross_attention.py:877-878) without the host sync.  loss f32 [1], acc f64 [2]. */
 int icka_loss_accumulate(const float* loss, double* acc, void* stream);
