@@ -85,6 +85,31 @@ extern const uint32_t* g_icka_nonce;   // set by icka_set_dropout_nonce (element
 // the CUs RCCL's workgroups may hold): every launch whose blocks wait for each other (the persistent BiLSTM, icka_gemm_ln)
 // is used only when its grid fits into the device's CUs minus this reserve.  Defined in elementwise.hip.
 extern int g_icka_reserved_cus;
+// CUs of the current device (256 on a whole MI355X, fewer in a partitioned mode), looked up once; 1 if the query fails.
+// The callers subtract g_icka_reserved_cus themselves.
+static inline int icka_device_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
+        else { n = 1; (void)hipGetLastError(); }
+    }
+    return n;
+}
+// Maps a zeroed 64-byte block of host memory into the device (an error word a kernel raises with one system-scope store and
+// the host reads as plain memory).  false, with the runtime's error cleared, if it cannot; never call inside a stream capture.
+static inline bool icka_map_host_words(volatile unsigned int** host, unsigned int** dev) {
+    void* h = nullptr;
+    void* d = nullptr;
+    if (hipHostMalloc(&h, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, h, 0) != hipSuccess || !d) {
+        (void)hipGetLastError();
+        return false;
+    }
+    for (int i = 0; i < 16; ++i) reinterpret_cast<volatile unsigned int*>(h)[i] = 0u;
+    *host = reinterpret_cast<volatile unsigned int*>(h);
+    *dev = reinterpret_cast<unsigned int*>(d);
+    return true;
+}
 __host__ __device__ __forceinline__ DropCfg make_drop(float p, uint64_t seed) {
     DropCfg d;
     d.s0 = (uint32_t)seed;

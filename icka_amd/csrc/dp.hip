@@ -119,16 +119,7 @@ extern "C" int icka_dp_cast_back_scaled(const void* src, float* dst, int64_t n, 
 /* Maps the host-visible error word (once; never call inside a stream capture). */
 extern "C" int icka_dp_init(void) {
     if (g_dp_err_dev) return 0;
-    void* h = nullptr;
-    void* d = nullptr;
-    if (hipHostMalloc(&h, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, h, 0) != hipSuccess || !d) {
-        (void)hipGetLastError();
-        return ICKA_E_ARG;
-    }
-    *reinterpret_cast<volatile unsigned int*>(h) = 0u;
-    g_dp_err_host = reinterpret_cast<volatile unsigned int*>(h);
-    g_dp_err_dev = reinterpret_cast<unsigned int*>(d);
-    return 0;
+    return icka_map_host_words(&g_dp_err_host, &g_dp_err_dev) ? 0 : ICKA_E_ARG;
 }
 extern "C" int icka_dp_error(void) { return g_dp_err_host ? (int)*g_dp_err_host : 0; }
 extern "C" int icka_dp_clear_error(void) {

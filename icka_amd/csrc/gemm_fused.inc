@@ -102,15 +102,6 @@ __global__ __launch_bounds__(512) void gemm_ln_kernel(const GemmLnArgs p) {
 
 }  // namespace
 
-static int device_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else { n = 1; (void)hipGetLastError(); }
-    }
-    return n;
-}
 constexpr int GEMM_LN_MAX_STRIPES = 64;
 static int g_gemm_ln_polls = 0;      // icka_gemm_ln_test_hooks: 0 = the default budget (~7 ms of s_sleep polls)
 static int g_gemm_ln_drop = -1;      // icka_gemm_ln_test_hooks: block that never arrives (-1: off)
@@ -141,7 +132,7 @@ extern "C" int icka_gemm_ln(const icka_gemm_desc* d, const float* bias, const vo
     const int stripes = g.M / BM;
     // (any number of stripes: where M / 128 is not a multiple of 8 a stripe's blocks spread over two or three XCDs -- the hand-off
     //  is write-through stores + agent-scope counter + L1-bypassing loads, correct under any placement, a little slower there)
-    if (!bnt || stripes < 1 || stripes > GEMM_LN_MAX_STRIPES || stripes * 8 > device_cus() - g_icka_reserved_cus) return ICKA_E_SHAPE;
+    if (!bnt || stripes < 1 || stripes > GEMM_LN_MAX_STRIPES || stripes * 8 > icka_device_cus() - g_icka_reserved_cus) return ICKA_E_SHAPE;
     if (g.N % 8 || ldy % 8 || (residual && ldr % 8) || g.ldc % 4) return ICKA_E_ALIGN;
     if ((int64_t)g.M * g.ldc * 4 >= (1ll << 31) - 64) return ICKA_E_SHAPE;      // 32-bit byte offsets of the raw buffer accesses
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };

@@ -5,45 +5,17 @@
 // torch.nn.LSTM.
 //
 // The input projection of all S steps and both directions is ONE GEMM of the GEMM kernels ([B*S, H] x [H, 8H], the
-// reference hoists nothing: cuDNN/ATen does the same internally).  This file holds the sequential part: one launch per
-// time step (both directions in the launch, captured in the step's hipGraph), a block per 16 hidden units:
-//   forward : G = h_{t-1} . W_hh^T for its 4 x 16 gate columns on the MFMA (one gate per wave, operands straight from
-//             L2 -- the 4H x H recurrent matrix is 4.7 MB and stays L2-resident), then the cell update for its units.
-//   backward: dh_rec = dgates_{t+1} . W_hh for its 16 units (K = 4H split over the 4 waves), then the gate
-//             derivatives of step t.  The weight / input gradients are GEMMs over all steps after the loop.
-// The state lives in the saved tensors: h_{t-1} is read from the output y, c_{t-1} from c_all.
-#include <math.h>
-
-#include "common.h"
+// reference hoists nothing: cuDNN/ATen does the same internally).  This file holds the sequential part, a block per 16
+// hidden units and direction: forward G = h_{t-1} . W_hh^T on the MFMA (operands straight from L2 -- the 4H x H recurrent
+// matrix is 4.7 MB and stays L2-resident), then the cell update; backward dh_rec = dgates_{t+1} . W_hh, then the gate
+// derivatives of step t (the weight / input gradients are GEMMs over all steps after the loop).  Three forms per
+// direction, chosen per call by the host code at the end of the file (ICKA_LSTM_* flags): one launch per time step with
+// the state in the saved tensors (*_step_kernel, any shape); ONE launch for all steps with a ticket barrier between them
+// (*_persistent_kernel); one launch with tagged data words (lstm_fwd_ll_kernel, lstm_bwd_rs_kernel: the default).
+// What the kernels share is lstm_core.h; here are the kernel bodies and the host side.
+#include "lstm_core.h"
 
 namespace {
-
-struct LstmArgs {
-    const float* gx; int64_t ldg;      // input projection + both biases, f32 [B*S, 8H]: col = dir*4H + gate*H + unit
-    const bf16_t* whh;                 // forward: [2][4H][H] (gate-row, k contiguous); backward: W_hh^T [2][H][4H]
-    bf16_t* y;                         // [B, S, 2H] hidden states (= LSTM output), col = dir*H + unit
-    float* c_all;                      // [B, S, 2, H] cell states
-    bf16_t* act;                       // [B, S, 2, 4H] gate activations i, f, g, o
-    bf16_t* hprev;                     // [B, S, 2H] h_{t-1} of every step (operand of the dW_hh GEMM), may be NULL
-    const bf16_t* dy;                  // [B, S, 2H] gradient of the output
-    bf16_t* dgates;                    // [B*S, 8H] gate pre-activation gradients
-    float* dc_carry;                   // [2, B, H] dc_{t+1} * f_{t+1}
-    int B, S, H, step;
-    int poll_limit;                    // persistent forms: polls before a hand-off wait gives up (error word + NaN poison)
-    int test_drop;                     // test hook (icka_lstm_test_hooks): block (0, 0, 0) does not publish this step; -1 = off
-};
-
-// 16-byte fragment of a k-contiguous row (8 bf16); zero when the row is invalid
-__device__ __forceinline__ bf16x8 frag16(const bf16_t* row, bool ok) {
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (ok) v = *reinterpret_cast<const u32x4*>(row);
-    return as_bf16x8(v);
-}
-
-constexpr int MAX_RT = 4;   // batch row tiles of 16 (B <= 64 per launch)
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-    return (uint32_t)__builtin_bit_cast(unsigned short, f2bf(lo)) | ((uint32_t)__builtin_bit_cast(unsigned short, f2bf(hi)) << 16);
-}
 
 // ---------------------------------------------------------------------------------------------------- forward step
 template <int NRT, int UB>
@@ -96,23 +68,15 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const LstmArgs a) {
                 for (int r = 0; r < NRT; ++r) acc[r] = mfma16(wf[u], hf[r][u], acc[r]);   // D[i = unit 4*g4 + q][j = batch i15]
         }
     }
-#pragma unroll
-    for (int r = 0; r < NRT; ++r)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s_g[wave][16 * r + i15][4 * g4 + q] = acc[r][q];
+    lstm_acc_to_lds(s_g[wave], acc, i15, g4);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NRT; ++i) {
         const int p = tid + 256 * i, b = p >> 4, u = p & 15;
         if (b >= a.B) continue;
         const int64_t row = (int64_t)b * S + tt;
-        const float gi = sigmoid_f(s_g[0][b][u] + gxr[i][0]);
-        const float gf = sigmoid_f(s_g[1][b][u] + gxr[i][1]);
-        const float gg = tanhf(s_g[2][b][u] + gxr[i][2]);
-        const float go = sigmoid_f(s_g[3][b][u] + gxr[i][3]);
-        const float cp = cpr[i];
-        const float c = gf * cp + gi * gg;
-        const float h = go * tanhf(c);
+        float gi, gf, gg, go, c;
+        const float h = lstm_cell_fwd([=, &gxr](int q) { return s_g[q][b][u] + gxr[i][q]; }, &cpr[i], gi, gf, gg, go, c);
         a.c_all[(row * 2 + d) * H + u0 + u] = c;
         a.y[row * 2 * H + (int64_t)d * H + u0 + u] = f2bf(h);
         bf16_t* act = a.act + (row * 2 + d) * 4 * H + u0 + u;
@@ -177,10 +141,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const LstmArgs a) {
                 for (int r = 0; r < NRT; ++r) acc[r] = mfma16(wf[u], gf[r][u], acc[r]);
         }
     }
-#pragma unroll
-    for (int r = 0; r < NRT; ++r)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s_p[wave][16 * r + i15][4 * g4 + q] = acc[r][q];
+    lstm_acc_to_lds(s_p[wave], acc, i15, g4);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NRT; ++i) {
@@ -210,50 +171,6 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const LstmArgs a) {
 // its direction have published step t.  All blocks are co-resident by construction (H/16 * 2 <= 256 blocks, one per
 // CU: checked on the host), so the barrier cannot deadlock; the spin is bounded anyway (it gives up after ~2^22 polls,
 // raises the error word and finishes with wrong data rather than hanging the device).
-struct LstmPersist {
-    unsigned int* tickets;   // [2] per-direction step counters, zeroed by the host before the launch
-    unsigned int* err;       // [1] set to 1 if a barrier wait gave up
-};
-
-// Hand-off form (cdna_hip_programming.md Guideline 16): the payload another block reads (h_t / dgates_t) is stored
-// WRITE-THROUGH with 8-byte agent-scope atomic stores (sc1), every storing wave drains its stores (s_waitcnt vmcnt(0)),
-// the block barrier joins them and ONE lane adds the ticket; the consumer polls with one lane, that lane issues ONE
-// agent-scope acquire (invalidates this CU's L1) and drains it, the block barrier releases the other waves to plain
-// loads.  No release fence (buffer_wbl2) and no per-thread __threadfence(): those made a step ~26 us.
-typedef __attribute__((address_space(1))) unsigned long long gu64_t;
-__device__ __forceinline__ void lstm_store_wt(void* p, unsigned long long v) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// A wait that gives up (a peer block that is not resident, a lost word) must not pass for a result: it raises the error
-// word -- host-visible memory when the library could map it (lstm_err_word), so the host reads it without a device
-// synchronisation -- and POISONS the recurrence: the waiting block continues with NaN operands, which reach every later
-// step of every block through h / dgates, so y, the loss and the gradients of the call are NaN.  Once poisoned a block no
-// longer spins (a failed launch costs one time-out, not one per step).
-__device__ __forceinline__ void lstm_raise(unsigned int* err) {
-    __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ float lstm_nan() { return __uint_as_float(0x7fc00000u); }
-// returns true (to every thread of the block) when the block is poisoned; ``s_poison`` is a __shared__ word zeroed at kernel start
-__device__ __forceinline__ bool lstm_grid_wait(unsigned int* ctr, unsigned int target, unsigned int* err, int limit,
-                                               int* s_poison) {
-    if (threadIdx.x == 0) {
-        int polls = 0;
-        if (*s_poison == 0)
-            while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                __builtin_amdgcn_s_sleep(2);
-                if (++polls > limit) { lstm_raise(err); *s_poison = 1; break; }
-            }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    return *s_poison != 0;
-}
-__device__ __forceinline__ void lstm_grid_signal(unsigned int* ctr) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its write-through stores
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 template <int NRT, int KS>
 __global__ __launch_bounds__(256) void lstm_fwd_persistent_kernel(const LstmArgs a, const LstmPersist ps) {
@@ -304,10 +221,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_persistent_kernel(const LstmArgs
             for (int u = 0; u < KS; ++u)
 #pragma unroll
                 for (int r = 0; r < NRT; ++r) acc[r] = mfma16(wf[u], hf[r][u], acc[r]);
-            if (bad) {
-#pragma unroll
-                for (int r = 0; r < NRT; ++r) acc[r] = f32x4{lstm_nan(), lstm_nan(), lstm_nan(), lstm_nan()};
-            }
+            if (bad) lstm_poison(acc);
         }
         __syncthreads();   // s_g of the previous step fully consumed
 #pragma unroll
@@ -320,12 +234,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_persistent_kernel(const LstmArgs
             const int p = tid + 256 * i, b = p >> 4, u = p & 15;
             if (b >= a.B) continue;
             const int64_t row = (int64_t)b * S + tt;
-            const float gi = sigmoid_f(s_g[0][b][u] + gxr[i][0]);
-            const float gf = sigmoid_f(s_g[1][b][u] + gxr[i][1]);
-            const float gg = tanhf(s_g[2][b][u] + gxr[i][2]);
-            const float go = sigmoid_f(s_g[3][b][u] + gxr[i][3]);
-            const float c = gf * creg[i] + gi * gg;
-            const float h = go * tanhf(c);
+            float gi, gf, gg, go, c;
+            const float h = lstm_cell_fwd([=, &gxr](int q) { return s_g[q][b][u] + gxr[i][q]; }, &creg[i], gi, gf, gg, go, c);
             if (a.hprev)   // h_{t-1} of this (b, u): still in s_h from the previous step (same thread wrote it)
                 a.hprev[row * 2 * H + (int64_t)d * H + u0 + u] = step == 0 ? f2bf(0.f) : s_h[b][u];
             creg[i] = c;
@@ -361,11 +271,6 @@ __global__ __launch_bounds__(256) void lstm_fwd_persistent_kernel(const LstmArgs
 constexpr int LSTM_LL_MAXH = 1024, LSTM_LL_ROWS = 16 * MAX_RT;
 __device__ unsigned long long g_lstm_ll[2 * 2 * LSTM_LL_ROWS * (LSTM_LL_MAXH / 2)];   // [parity][dir][b][H / 2]
 
-__device__ __forceinline__ u32x4 ll_load16(const unsigned long long* p) {
-    u32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-    return v;
-}
 
 template <int NRT, int KQ>   // KQ = W_hh fragments per gate and wave = H / 128
 __global__ __launch_bounds__(256) void lstm_fwd_ll_kernel(const LstmArgs a, unsigned int* err) {
@@ -472,9 +377,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_ll_kernel(const LstmArgs a, unsi
                     for (int q = 0; q < 4; ++q) acc[r][q] = mfma16(wf[q][u], hf[r][u], acc[r][q]);
             if (poison) {
 #pragma unroll
-                for (int r = 0; r < NRT; ++r)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[r][q] = f32x4{lstm_nan(), lstm_nan(), lstm_nan(), lstm_nan()};
+                for (int r = 0; r < NRT; ++r) lstm_poison(acc[r]);
             }
         }
         __syncthreads();   // s_g / s_h of the previous step fully consumed
@@ -582,10 +485,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_persistent_kernel(const LstmArgs
             for (int u = 0; u < KS; ++u)
 #pragma unroll
                 for (int r = 0; r < NRT; ++r) acc[r] = mfma16(wf[u], gf[r][u], acc[r]);
-            if (bad) {
-#pragma unroll
-                for (int r = 0; r < NRT; ++r) acc[r] = f32x4{lstm_nan(), lstm_nan(), lstm_nan(), lstm_nan()};
-            }
+            if (bad) lstm_poison(acc);
         }
         __syncthreads();
 #pragma unroll
@@ -597,16 +497,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_persistent_kernel(const LstmArgs
         for (int i = 0; i < NRT; ++i) {
             const int p = tid + 256 * i, b = p >> 4, u = p & 15;
             if (b >= a.B) continue;
-            (void)tt;
             const float dh = dyr[i] + (s_p[0][b][u] + s_p[1][b][u] + s_p[2][b][u] + s_p[3][b][u]);
-            const float gi = actr[i][0], gf = actr[i][1], gg = actr[i][2], go = actr[i][3];
-            const float tc = tanhf(cr[i]);
-            const float dc = dh * go * (1.f - tc * tc) + carry[i];
-            carry[i] = dc * gf;
-            s_dg[0][b][u] = f2bf(dc * gg * gi * (1.f - gi));
-            s_dg[1][b][u] = f2bf(dc * cpr[i] * gf * (1.f - gf));
-            s_dg[2][b][u] = f2bf(dc * gi * (1.f - gg * gg));
-            s_dg[3][b][u] = f2bf(dh * tc * go * (1.f - go));
+            carry[i] = lstm_cell_bwd(dh, actr[i], cr[i], cpr[i], carry[i], s_dg[0][b][u], s_dg[1][b][u], s_dg[2][b][u], s_dg[3][b][u]);
         }
         __syncthreads();
         // publish dgates_t: 4 units (8 bytes) per store, write-through
@@ -715,14 +607,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_rs_kernel(const LstmArgs a, unsi
         __syncthreads();
         if (crow) {
             const float dh = dyr + ((s_p[0][cb][cu] + s_p[1][cb][cu]) + (s_p[2][cb][cu] + s_p[3][cb][cu]));
-            const float gi = actr[0], gf = actr[1], gg = actr[2], go = actr[3];
-            const float tc = tanhf(cr);
-            const float dc = dh * go * (1.f - tc * tc) + carry;
-            carry = dc * gf;
-            s_dg[0][cb][cu] = f2bf(dc * gg * gi * (1.f - gi));
-            s_dg[1][cb][cu] = f2bf(dc * cpr * gf * (1.f - gf));
-            s_dg[2][cb][cu] = f2bf(dc * gi * (1.f - gg * gg));
-            s_dg[3][cb][cu] = f2bf(dh * tc * go * (1.f - go));
+            carry = lstm_cell_bwd(dh, actr, cr, cpr, carry, s_dg[0][cb][cu], s_dg[1][cb][cu], s_dg[2][cb][cu], s_dg[3][cb][cu]);
         } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q) s_dg[q][cb][cu] = f2bf(0.f);
@@ -769,14 +654,16 @@ __global__ __launch_bounds__(256) void lstm_bwd_rs_kernel(const LstmArgs a, unsi
 // (dp.GradReducer) -- cannot take one until that workgroup exits: the grid is no longer co-resident by construction and
 // its blocks would spin on a peer that has not started.  The reducer reserves as many CUs as RCCL runs channels.
 static int lstm_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else { n = 1; (void)hipGetLastError(); }
-    }
-    const int avail = n - g_icka_reserved_cus;
+    const int avail = icka_device_cus() - g_icka_reserved_cus;
     return avail > 0 ? avail : 0;
+}
+// true while work issued to `st` is recorded into a graph instead of running (nothing may be allocated, no event recorded or
+// waited for); a query that fails counts as capturing and its error is cleared.  The legacy default stream cannot be captured.
+static bool lstm_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (st == nullptr) return false;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return true; }
+    return cs != hipStreamCaptureStatusNone;
 }
 // Which form a call takes is decided PER CALL by its ``flags`` argument (ICKA_LSTM_*, include/icka_hip.h): the default (0) is
 // the persistent launch with the flag-in-data hand-off and batch tiles of 16 rows as separate blocks; there is no process-wide
@@ -787,8 +674,7 @@ static unsigned long long* lstm_rs_words(hipStream_t st) {   // [2 parity][2 dir
     if (!p && !failed) {
         // never allocate while the stream is being captured into a graph (hipMalloc would invalidate the capture): the
         // caller then uses the ticket form for this launch; the first eager launch allocates
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
+        if (lstm_capturing(st)) return nullptr;
         if (hipMalloc((void**)&p, sizeof(unsigned long long) * 4 * 64 * 64 * 256) != hipSuccess) { p = nullptr; failed = true; (void)hipGetLastError(); }
     }
     return p;
@@ -814,21 +700,9 @@ static bool g_lstm_fallback_used = false;   // a launch was given the device wor
 static unsigned int* lstm_err_word(hipStream_t st) {
     if (g_lstm_err_dev) return g_lstm_err_dev;
     static bool failed = false;
-    if (!failed) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = st != nullptr && (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone);
-        if (!capturing) {
-            void* h = nullptr;
-            void* d = nullptr;
-            if (hipHostMalloc(&h, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess && d) {
-                *reinterpret_cast<volatile unsigned int*>(h) = 0u;
-                g_lstm_err_host = reinterpret_cast<volatile unsigned int*>(h);
-                g_lstm_err_dev = reinterpret_cast<unsigned int*>(d);
-                return g_lstm_err_dev;
-            }
-            failed = true;
-            (void)hipGetLastError();
-        }
+    if (!failed && !lstm_capturing(st)) {
+        if (icka_map_host_words(&g_lstm_err_host, &g_lstm_err_dev)) return g_lstm_err_dev;
+        failed = true;
     }
     unsigned int* base = lstm_sync_words();
     g_lstm_fallback_used = true;
@@ -842,11 +716,7 @@ static unsigned int* lstm_err_word(hipStream_t st) {
 struct LstmTurn {
     hipStream_t st;
     bool eager;
-    explicit LstmTurn(hipStream_t s) : st(s), eager(false) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        // (the legacy default stream cannot be captured)
-        if (st != nullptr && hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return; }
-        eager = cs == hipStreamCaptureStatusNone;
+    explicit LstmTurn(hipStream_t s) : st(s), eager(!lstm_capturing(s)) {
         if (eager && s_event && s_last != st) (void)hipStreamWaitEvent(st, s_event, 0);
     }
     ~LstmTurn() {
@@ -859,10 +729,19 @@ struct LstmTurn {
 };
 hipEvent_t LstmTurn::s_event = nullptr;
 hipStream_t LstmTurn::s_last = nullptr;
-int g_lstm_poll_limit = 0;    // icka_lstm_test_hooks: 0 = the per-form defaults below
+int g_lstm_poll_limit = 0;    // icka_lstm_test_hooks: 0 = the per-form defaults (lstm_persist_begin)
 int g_lstm_test_drop = -1;    // icka_lstm_test_hooks
-static int lstm_poll_limit(int dflt) { return g_lstm_poll_limit > 0 ? g_lstm_poll_limit : dflt; }
+// Every persistent launch, once it holds its LstmTurn: sets the poll budget (the test hook's, else the form's default) and
+// clears the hand-off words of an earlier launch.  Returns the error word for the kernel, or nullptr: the launch is refused.
+static unsigned int* lstm_persist_begin(LstmArgs& a, hipStream_t st, void* words, size_t bytes, int polls) {
+    unsigned int* errw = lstm_err_word(st);
+    if (!errw || !words) return nullptr;
+    a.poll_limit = g_lstm_poll_limit > 0 ? g_lstm_poll_limit : polls;
+    return hipMemsetAsync(words, 0, bytes, st) == hipSuccess ? errw : nullptr;
+}
 
+// ==== Not part of the recurrence: two small kernels on the same operands-from-L2 scheme.  They stay in this unit: taking
+// them out moves the word buffer g_lstm_ll against the code and with it an address literal in every lstm_fwd_ll_kernel.
 // W^T for both directions: in [2][R][C] -> out [2][C][R] (bf16), 32x32 tiles through LDS
 __global__ __launch_bounds__(256) void transpose_kernel(const bf16_t* __restrict__ in, bf16_t* __restrict__ out, int R,
                                                         int C) {
@@ -916,10 +795,7 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const SmallLinArgs a)
 #pragma unroll
             for (int r = 0; r < NRT; ++r) acc[r] = mfma16(wf[u], xf[r][u], acc[r]);   // D[i = column 4*g4+q][j = row i15]
     }
-#pragma unroll
-    for (int r = 0; r < NRT; ++r)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s_p[wave][16 * r + i15][4 * g4 + q] = acc[r][q];
+    lstm_acc_to_lds(s_p[wave], acc, i15, g4);
     __syncthreads();
     for (int p = tid; p < NRT * 256; p += 256) {
         const int m = p >> 4, u = p & 15;
@@ -929,6 +805,7 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const SmallLinArgs a)
         a.y[(int64_t)m * a.ldy + n0 + u] = f2bf(v);
     }
 }
+
 
 inline int lstm_check(int B, int S, int H) {
     if (B <= 0 || S <= 0 || H <= 0) return ICKA_E_SHAPE;
@@ -955,12 +832,9 @@ extern "C" int icka_lstm_fwd(const float* gates_x, int64_t ldg, const void* w_hh
     if (persistent && handoff == 1 && nrt <= 2 && H <= LSTM_LL_MAXH && H % 128 == 0 && (H / 16) * 2 <= lstm_cus()) {
         // flag-in-data hand-off: zero the word buffers (tags of an earlier launch), then one launch for all S steps
         hipStream_t st = (hipStream_t)stream;
-        unsigned int* errw = lstm_err_word(st);
-        unsigned long long* ll = lstm_ll_words();
-        if (!errw || !ll) return ICKA_E_ARG;
         LstmTurn turn(st);
-        a.poll_limit = lstm_poll_limit(1 << 20);
-        if (hipMemsetAsync(ll, 0, sizeof(unsigned long long) * 2 * 2 * LSTM_LL_ROWS * (LSTM_LL_MAXH / 2), st) != hipSuccess) return ICKA_E_ARG;
+        unsigned int* errw = lstm_persist_begin(a, st, lstm_ll_words(), sizeof(unsigned long long) * 2 * 2 * LSTM_LL_ROWS * (LSTM_LL_MAXH / 2), 1 << 20);
+        if (!errw) return ICKA_E_ARG;
         // batch rows are independent recurrences: two tiles of 16 rows run as separate blocks (grid.z) where all of them
         // are co-resident -- half the words to poll and half the MFMAs per block and step
         const bool split = bsplit && nrt == 2 && (H / 16) * 2 * 2 <= lstm_cus();
@@ -981,14 +855,11 @@ extern "C" int icka_lstm_fwd(const float* gates_x, int64_t ldg, const void* w_hh
     }
 ticket_form:
     if (persistent && nrt <= 2 && H <= 1024 && (H / 16) * 2 <= lstm_cus()) {
-        LstmPersist ps;
-        unsigned int* base = lstm_sync_words();
-        unsigned int* errw = lstm_err_word((hipStream_t)stream);
-        if (!base || !errw) return ICKA_E_ARG;
-        ps.tickets = base; ps.err = errw;
         LstmTurn turn((hipStream_t)stream);
-        a.poll_limit = lstm_poll_limit(1 << 22);
-        if (hipMemsetAsync(base, 0, 4 * sizeof(unsigned int), (hipStream_t)stream) != hipSuccess) return ICKA_E_ARG;
+        LstmPersist ps;
+        ps.tickets = lstm_sync_words();
+        ps.err = lstm_persist_begin(a, (hipStream_t)stream, ps.tickets, 4 * sizeof(unsigned int), 1 << 22);
+        if (!ps.err) return ICKA_E_ARG;
         // KS = resident W_hh fragments per wave (32 hidden units each): 24 up to H = 768, 32 up to H = 1024
         if (H > 768) {
             if (nrt == 1) hipLaunchKernelGGL((lstm_fwd_persistent_kernel<1, 32>), dim3(H / 16, 2), dim3(256), 0, (hipStream_t)stream, a, ps);
@@ -1024,14 +895,13 @@ extern "C" int icka_lstm_bwd(const void* dy, const void* w_hh_t, const void* act
     const int nrt = (B + 15) / 16;
     if (persistent && handoff == 1 && nrt <= 2 && H <= LSTM_LL_MAXH && H % 256 == 0 && (H / 16) * 2 * nrt <= lstm_cus()) {
         // reduce-scatter form with tagged words (lstm_bwd_rs_kernel); the word buffer is allocated once (largest shape)
-        unsigned int* errw = lstm_err_word((hipStream_t)stream);
-        unsigned long long* llr = lstm_rs_words((hipStream_t)stream);
-        if (errw && llr) {
-            hipStream_t st = (hipStream_t)stream;
-            LstmTurn turn(st);
-            a.poll_limit = lstm_poll_limit(1 << 17);
+        hipStream_t st = (hipStream_t)stream;
+        unsigned long long* llr = lstm_rs_words(st);
+        if (llr) {   // (none inside a stream capture before the first eager launch: the ticket form below)
             const int nblk = H / 16;
-            if (hipMemsetAsync(llr, 0, sizeof(unsigned long long) * 4 * nblk * nblk * 256, st) != hipSuccess) return ICKA_E_ARG;
+            LstmTurn turn(st);
+            unsigned int* errw = lstm_persist_begin(a, st, llr, sizeof(unsigned long long) * 4 * nblk * nblk * 256, 1 << 17);
+            if (!errw) return ICKA_E_ARG;
             const dim3 grid(nblk, 2, nrt);
             switch (H / 256) {
                 case 1: hipLaunchKernelGGL((lstm_bwd_rs_kernel<4>), grid, dim3(256), 0, st, a, llr, errw); break;
@@ -1044,14 +914,11 @@ extern "C" int icka_lstm_bwd(const void* dy, const void* w_hh_t, const void* act
         }
     }
     if (persistent && nrt <= 2 && H <= 1024 && (H / 16) * 2 <= lstm_cus()) {
-        LstmPersist ps;
-        unsigned int* base = lstm_sync_words();
-        unsigned int* errw = lstm_err_word((hipStream_t)stream);
-        if (!base || !errw) return ICKA_E_ARG;
-        ps.tickets = base; ps.err = errw;
         LstmTurn turn((hipStream_t)stream);
-        a.poll_limit = lstm_poll_limit(1 << 22);
-        if (hipMemsetAsync(base, 0, 4 * sizeof(unsigned int), (hipStream_t)stream) != hipSuccess) return ICKA_E_ARG;
+        LstmPersist ps;
+        ps.tickets = lstm_sync_words();
+        ps.err = lstm_persist_begin(a, (hipStream_t)stream, ps.tickets, 4 * sizeof(unsigned int), 1 << 22);
+        if (!ps.err) return ICKA_E_ARG;
         // (batch tiles as separate blocks, as in the forward launch, are slower here: 9.3 vs 8.9 us per step at H = 768 --
         //  every block reads all of dgates_t through L2 either way, twice the blocks only add contention)
         if (H > 768) {
