@@ -11,7 +11,7 @@ from .modeling import (BertAttention, BertCoAttention, BertCrossAttention, BertC
                        resolved_precision, set_precision, token_ce_loss)
 from .arena import ParamArena
 from .crf import CRF, ConstrainedPaths, NBestPaths, SampledPaths, minimum_risk
-from .lstm import BiLSTM
+from .lstm import BiLSTM, set_length_aware
 from .modeling import MTCCMBertForMMTokenClassificationCRF_gate_1
 from .dp import GradReducer
 from . import graph
@@ -26,7 +26,7 @@ from .metrics import ChunkEvaluator
 from .entities import EntityDecoder, NBestEntities
 from .attention_maps import attention_maps   # (the name now denotes the recorder; the module stays importable by its path)
 
-__all__ = ["CRF", "BiLSTM", "MTCCMBertForMMTokenClassificationCRF_gate_1", "BertConfig", "BertModel", "BertEmbeddings", "BertEncoder", "BertLayer", "BertLayerNorm", "BertPooler",
+__all__ = ["CRF", "BiLSTM", "set_length_aware", "MTCCMBertForMMTokenClassificationCRF_gate_1", "BertConfig", "BertModel", "BertEmbeddings", "BertEncoder", "BertLayer", "BertLayerNorm", "BertPooler",
            "BertSelfEncoder", "BertCrossEncoder", "BertCrossAttentionLayer", "BertAttention", "BertCrossAttention",
            "BertSelfAttention", "BertCoAttention", "BertSelfOutput", "BertIntermediate", "BertOutput",
            "BertPreTrainedModel", "MTCCMBertForMMTokenClassificationCRF", "cls_layer_both", "scalar_gate_fusion",

@@ -300,7 +300,10 @@ class MTCCMBertForMMTokenClassificationCRF(BertPreTrainedModel):
             result = scalar_gate_fusion(self, cross_gate.view(B, S, H), token_embedding)
         else:
             result = _scalar_gate(self, A, cross_gate, token_embedding.view(B * S, H), B, S)
-        x, _ = self.lstm(result.view(B, S, H))
+        # set_length_aware: packed-sequence semantics, the lengths read from the text mask on the device
+        from .lstm import lengths_of_mask
+        lengths = lengths_of_mask(ori_input_mask) if self.lstm.length_aware else None
+        x, _ = self.lstm(result.view(B, S, H), lengths=lengths)
         if ex:
             em = X.LinearFn.apply(A.anchor, x.reshape(B * S, 2 * H), self.classifier, A, False)
         else:

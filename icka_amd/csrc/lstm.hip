@@ -13,6 +13,10 @@
 // the state in the saved tensors (*_step_kernel, any shape); ONE launch for all steps with a ticket barrier between them
 // (*_persistent_kernel); one launch with tagged data words (lstm_fwd_ll_kernel, lstm_bwd_rs_kernel: the default).
 // What the kernels share is lstm_core.h; here are the kernel bodies and the host side.
+// Variable lengths (icka_lstm_fwd_varlen, contract in include/icka_hip.h): bf16 mode masks by a SELECT WHERE THE FORWARD KERNELS
+// LOAD gates_x (lstm_core.h: LSTM_PAD_GATE), every form walks all S steps, the backward kernels need nothing; fp32 mode
+// (exact.hip) masks its f32 gate buffer in place with lstm_mask_gates_kernel below.  All forms, the per-step ones (ICKA_LSTM_
+// PER_STEP, B > 32, H > 1024) included, are correct under lengths and none is faster for them.
 #include "lstm_core.h"
 
 namespace {
@@ -36,8 +40,10 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const LstmArgs a) {
         const int p = tid + 256 * i, b = p >> 4, u = p & 15;
         const bool ok = b < a.B;
         const float* gx = a.gx + ((int64_t)(ok ? b : 0) * S + tt) * a.ldg + (int64_t)d * 4 * H + u0 + u;
+        const bool pad = tt >= lstm_len(a.lens, ok ? b : 0, S);
 #pragma unroll
         for (int q = 0; q < 4; ++q) gxr[i][q] = gx[q * H];
+        if (pad) gxr[i][0] = gxr[i][1] = LSTM_PAD_GATE;
         cpr[i] = first ? 0.f : a.c_all[(((int64_t)(ok ? b : 0) * S + tp) * 2 + d) * H + u0 + u];
     }
     f32x4 acc[NRT];
@@ -190,8 +196,13 @@ __global__ __launch_bounds__(256) void lstm_fwd_persistent_kernel(const LstmArgs
         for (int u = 0; u < KS; ++u) wf[u] = frag16(wrow + 32 * u, 32 * u < H);
     }
     float creg[NRT];   // cell state of this thread's (b, u) pairs
+    int lenr[NRT];     // ... and the length of their rows
 #pragma unroll
-    for (int i = 0; i < NRT; ++i) creg[i] = 0.f;
+    for (int i = 0; i < NRT; ++i) {
+        creg[i] = 0.f;
+        const int b = (tid + 256 * i) >> 4;
+        lenr[i] = lstm_len(a.lens, b < a.B ? b : 0, S);
+    }
     for (int step = 0; step < S; ++step) {
         const int tt = d == 0 ? step : S - 1 - step;
         const int tp = d == 0 ? tt - 1 : tt + 1;
@@ -200,8 +211,10 @@ __global__ __launch_bounds__(256) void lstm_fwd_persistent_kernel(const LstmArgs
         for (int i = 0; i < NRT; ++i) {
             const int p = tid + 256 * i, b = p >> 4, u = p & 15;
             const float* gx = a.gx + ((int64_t)(b < a.B ? b : 0) * S + tt) * a.ldg + (int64_t)d * 4 * H + u0 + u;
+            const bool pad = tt >= lenr[i];
 #pragma unroll
             for (int q = 0; q < 4; ++q) gxr[i][q] = gx[q * H];
+            if (pad) gxr[i][0] = gxr[i][1] = LSTM_PAD_GATE;
         }
         f32x4 acc[NRT];
 #pragma unroll
@@ -289,8 +302,13 @@ __global__ __launch_bounds__(256) void lstm_fwd_ll_kernel(const LstmArgs a, unsi
         for (int u = 0; u < KQ; ++u) wf[q][u] = frag16(wrow + 32 * u, true);
     }
     float creg[NRT];
+    int lenr[NRT];   // length of the row of each of this thread's (b, u) pairs
 #pragma unroll
-    for (int i = 0; i < NRT; ++i) creg[i] = 0.f;
+    for (int i = 0; i < NRT; ++i) {
+        creg[i] = 0.f;
+        const int b = (tid + 256 * i) >> 4;
+        lenr[i] = lstm_len(a.lens, b + bofs < a.B ? b + bofs : 0, S);
+    }
     bool poison = false;   // wave-uniform: a wait of this wave gave up (lstm_raise); NaN operands from then on, no more spinning
     for (int step = 0; step < S; ++step) {
         const int tt = d == 0 ? step : S - 1 - step;
@@ -299,8 +317,10 @@ __global__ __launch_bounds__(256) void lstm_fwd_ll_kernel(const LstmArgs a, unsi
         for (int i = 0; i < NRT; ++i) {
             const int p = tid + 256 * i, b = p >> 4, u = p & 15;
             const float* gx = a.gx + ((int64_t)(b + bofs < a.B ? b + bofs : 0) * S + tt) * a.ldg + (int64_t)d * 4 * H + u0 + u;
+            const bool pad = tt >= lenr[i];
 #pragma unroll
             for (int q = 0; q < 4; ++q) gxr[i][q] = gx[q * H];
+            if (pad) gxr[i][0] = gxr[i][1] = LSTM_PAD_GATE;
         }
         f32x4 acc[NRT][4];
 #pragma unroll
@@ -807,6 +827,19 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const SmallLinArgs a)
 }
 
 
+// The mask as a pass of its own, for a caller whose recurrence is not one of the kernels above (the fp32 mode, exact.hip: its
+// gate buffer has the layout of gates_x): the i and f pre-activations of both directions at every t >= len[b], in place.
+__global__ __launch_bounds__(256) void lstm_mask_gates_kernel(float* __restrict__ gx, int64_t ldg, const int32_t* __restrict__ lens,
+                                                              int S, int H) {
+    const int t = blockIdx.x, b = blockIdx.y;
+    if (t < lstm_len(lens, b, S)) return;
+    float* row = gx + ((int64_t)b * S + t) * ldg;
+    for (int j = threadIdx.x; j < 4 * H; j += 256) {   // j -> (direction, gate i / f, unit)
+        const int d = j / (2 * H), r = j - d * 2 * H;
+        row[(int64_t)d * 4 * H + r] = LSTM_PAD_GATE;
+    }
+}
+
 inline int lstm_check(int B, int S, int H) {
     if (B <= 0 || S <= 0 || H <= 0) return ICKA_E_SHAPE;
     if (B > 16 * MAX_RT || H % 32 != 0) return ICKA_E_SHAPE;
@@ -815,8 +848,9 @@ inline int lstm_check(int B, int S, int H) {
 
 }  // namespace
 
-extern "C" int icka_lstm_fwd(const float* gates_x, int64_t ldg, const void* w_hh, void* y, float* c_all, void* act,
-                             void* hprev, int32_t B, int32_t S, int32_t H, int32_t flags, void* stream) {
+extern "C" int icka_lstm_fwd_varlen(const float* gates_x, int64_t ldg, const void* w_hh, void* y, float* c_all, void* act,
+                                    void* hprev, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t flags,
+                                    void* stream) {
     if (!gates_x || !w_hh || !y || !c_all || !act) return ICKA_E_ARG;
     if (flags & ~(ICKA_LSTM_PER_STEP | ICKA_LSTM_TICKETS | ICKA_LSTM_NO_BATCH_SPLIT)) return ICKA_E_ARG;
     const int persistent = !(flags & ICKA_LSTM_PER_STEP), handoff = !(flags & ICKA_LSTM_TICKETS),
@@ -827,6 +861,7 @@ extern "C" int icka_lstm_fwd(const float* gates_x, int64_t ldg, const void* w_hh
     LstmArgs a{};
     a.gx = gates_x; a.ldg = ldg; a.whh = (const bf16_t*)w_hh; a.y = (bf16_t*)y; a.c_all = c_all;
     a.act = (bf16_t*)act; a.hprev = (bf16_t*)hprev; a.B = B; a.S = S; a.H = H;
+    a.lens = lens;
     a.test_drop = g_lstm_test_drop;
     const int nrt = (B + 15) / 16;
     if (persistent && handoff == 1 && nrt <= 2 && H <= LSTM_LL_MAXH && H % 128 == 0 && (H / 16) * 2 <= lstm_cus()) {
@@ -879,8 +914,14 @@ ticket_form:
     return 0;
 }
 
-extern "C" int icka_lstm_bwd(const void* dy, const void* w_hh_t, const void* act, const float* c_all, void* dgates,
-                             int64_t ldg, float* dc_carry, int32_t B, int32_t S, int32_t H, int32_t flags, void* stream) {
+extern "C" int icka_lstm_fwd(const float* gates_x, int64_t ldg, const void* w_hh, void* y, float* c_all, void* act,
+                             void* hprev, int32_t B, int32_t S, int32_t H, int32_t flags, void* stream) {
+    return icka_lstm_fwd_varlen(gates_x, ldg, w_hh, y, c_all, act, hprev, nullptr, B, S, H, flags, stream);
+}
+
+extern "C" int icka_lstm_bwd_varlen(const void* dy, const void* w_hh_t, const void* act, const float* c_all, void* dgates,
+                                    int64_t ldg, float* dc_carry, const int32_t* lens, int32_t B, int32_t S, int32_t H,
+                                    int32_t flags, void* stream) {
     if (!dy || !w_hh_t || !act || !c_all || !dgates || !dc_carry) return ICKA_E_ARG;
     if (flags & ~(ICKA_LSTM_PER_STEP | ICKA_LSTM_TICKETS | ICKA_LSTM_NO_BATCH_SPLIT)) return ICKA_E_ARG;
     const int persistent = !(flags & ICKA_LSTM_PER_STEP), handoff = !(flags & ICKA_LSTM_TICKETS);
@@ -891,6 +932,7 @@ extern "C" int icka_lstm_bwd(const void* dy, const void* w_hh_t, const void* act
     a.dy = (const bf16_t*)dy; a.whh = (const bf16_t*)w_hh_t; a.act = (bf16_t*)const_cast<void*>(act);
     a.c_all = const_cast<float*>(c_all); a.dgates = (bf16_t*)dgates; a.ldg = ldg; a.dc_carry = dc_carry;
     a.B = B; a.S = S; a.H = H;
+    a.lens = lens;   // (not read: the saved activations have i = f = 0 at the pads, which zeroes every gate gradient there)
     a.test_drop = g_lstm_test_drop;
     const int nrt = (B + 15) / 16;
     if (persistent && handoff == 1 && nrt <= 2 && H <= LSTM_LL_MAXH && H % 256 == 0 && (H / 16) * 2 * nrt <= lstm_cus()) {
@@ -936,6 +978,21 @@ extern "C" int icka_lstm_bwd(const void* dy, const void* w_hh_t, const void* act
         else hipLaunchKernelGGL((lstm_bwd_step_kernel<4, 8>), dim3(H / 16, 2), dim3(256), 0, (hipStream_t)stream, a);
         ICKA_CHECK_LAUNCH();
     }
+    return 0;
+}
+
+extern "C" int icka_lstm_bwd(const void* dy, const void* w_hh_t, const void* act, const float* c_all, void* dgates,
+                             int64_t ldg, float* dc_carry, int32_t B, int32_t S, int32_t H, int32_t flags, void* stream) {
+    return icka_lstm_bwd_varlen(dy, w_hh_t, act, c_all, dgates, ldg, dc_carry, nullptr, B, S, H, flags, stream);
+}
+
+extern "C" int icka_lstm_mask_gates(float* gates_x, int64_t ldg, const int32_t* lens, int32_t B, int32_t S, int32_t H,
+                                    void* stream) {
+    if (!gates_x || !lens) return ICKA_E_ARG;
+    if (B <= 0 || S <= 0 || H <= 0) return ICKA_E_SHAPE;
+    if (ldg < 8 * (int64_t)H) return ICKA_E_ARG;
+    hipLaunchKernelGGL(lstm_mask_gates_kernel, dim3(S, B), dim3(256), 0, (hipStream_t)stream, gates_x, ldg, lens, S, H);
+    ICKA_CHECK_LAUNCH();
     return 0;
 }
 

@@ -25,8 +25,20 @@ struct LstmArgs {
     int B, S, H, step;
     int poll_limit;                    // persistent forms: polls before a hand-off wait gives up (error word + NaN poison)
     int test_drop;                     // test hook (icka_lstm_test_hooks): block (0, 0, 0) does not publish this step; -1 = off
+    const int32_t* lens;               // [B] sequence lengths on the device (icka_lstm_*_varlen), NULL = every row has S steps
 };
 
+// ---- sequence lengths (icka_lstm_fwd_varlen / icka_lstm_bwd_varlen; include/icka_hip.h states the contract)
+// A kernel reads the lengths of its rows ONCE, at its start, clamped to [0, S]; no host value derived from them enters a
+// launch.  Positions t >= len[b] are pads: the forward kernels replace the i and f pre-activations they load from gates_x
+// by LSTM_PAD_GATE there (a select at the load, the cell code is untouched): sigmoid_f gives exactly 0, so c = 0 and h = 0
+// exactly, and the backward's gate gradients are exactly 0 without knowing about lengths at all.
+constexpr float LSTM_PAD_GATE = -1e4f;
+__device__ __forceinline__ int lstm_len(const int32_t* lens, int b, int S) {
+    if (!lens) return S;
+    const int v = lens[b];
+    return v < 0 ? 0 : (v > S ? S : v);
+}
 // 16-byte fragment of a k-contiguous row (8 bf16); zero when the row is invalid
 __device__ __forceinline__ bf16x8 frag16(const bf16_t* row, bool ok) {
     u32x4 v = {0u, 0u, 0u, 0u};

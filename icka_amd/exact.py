@@ -734,7 +734,7 @@ class LstmFn(torch.autograd.Function):
     input gradients as GEMMs and column sums over all steps."""
 
     @staticmethod
-    def forward(ctx, anchor, x, mod, A: ParamArena, B: int, S: int):
+    def forward(ctx, anchor, x, mod, A: ParamArena, B: int, S: int, lens=None):
         H = mod.hidden_size
         M = B * S
         lib = _lib.load()
@@ -745,6 +745,12 @@ class LstmFn(torch.autograd.Function):
         check(lib.icka_x_add(bi.data_ptr(), 8 * H, bh.data_ptr(), 8 * H, bsum.data_ptr(), 8 * H, 1, 8 * H, _stream()),
               "icka_x_add")
         gates = gemm(GEMM_NT, x, _fw(A, wih), _new(x, M, 8 * H), bias=bsum.view(-1))
+        if lens is not None:
+            # variable lengths (icka_hip.h: icka_lstm_fwd_varlen): i and f pre-activations := -1e4 at every t >= lens[b], in place;
+            # the per-step loop below runs all S steps on it (same results as a packed nn.LSTM, no step saved) and the backward
+            # finds exactly zero gate gradients at the pads without knowing the lengths
+            check(lib.icka_lstm_mask_gates(gates.data_ptr(), gates.stride(0), lens.data_ptr(), B, S, H, _stream()),
+                  "icka_lstm_mask_gates")
         y, c_all, hprev = _new(x, M, 2 * H), _new(x, M, 2 * H), _new(x, M, 2 * H)
         for k in range(S):
             if k:
@@ -788,7 +794,7 @@ class LstmFn(torch.autograd.Function):
             colsum(dgates, A.g_cat(bs), accumulate=A.grad_beta(bs) > 0)
         dx = gemm(GEMM_NN, dgates, _fw(A, wih), torch.empty_like(x)) if ctx.need_dx else None
         A.flush_final()
-        return None, dx, None, None, None, None
+        return None, dx, None, None, None, None, None
 
 
 class PromptEmbeddingsFn(torch.autograd.Function):

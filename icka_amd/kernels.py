@@ -856,9 +856,18 @@ def attn_bwd_packed(q, k, v, add_mask, dout, lse, delta, dq, dk, dv, cu, kv_pack
 
 
 # ------------------------------------------------------------------------------------------------- LSTM
-def lstm_fwd(gates_x, w_hh, y, c_all, act, hprev, B, S, H, flags=0):
+def _lstm_lens(lens, B, like):
+    """``lens`` of the variable-length LSTM entries: int32 [B], contiguous, on the device of the other operands."""
+    _dev(lens, "lens")
+    if lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous() or lens.device != like.device:
+        raise ValueError("lens must be a contiguous int32 [B] tensor on %s" % like.device)
+    return lens.data_ptr()
+
+
+def lstm_fwd(gates_x, w_hh, y, c_all, act, hprev, B, S, H, flags=0, lens=None):
     """gates_x f32 [B*S, 8H]; w_hh bf16 [8H, H] (= [2][4H][H]); y bf16 [B*S, 2H]; c_all f32 [B*S, 2H];
-    act bf16 [B*S, 8H]; hprev bf16 [B*S, 2H] or None."""
+    act bf16 [B*S, 8H]; hprev bf16 [B*S, 2H] or None.  ``lens`` (int32 [B] on the device): positions t >= lens[b] are pads
+    (icka_hip.h: icka_lstm_fwd_varlen); None is the fixed-length entry."""
     _dev(gates_x, "gates_x")
     if gates_x.dtype != F32 or gates_x.stride(1) != 1 or tuple(gates_x.shape) != (B * S, 8 * H):
         raise ValueError("gates_x must be f32 [B*S, 8H]")
@@ -867,17 +876,38 @@ def lstm_fwd(gates_x, w_hh, y, c_all, act, hprev, B, S, H, flags=0):
         _dev(t, n)
         if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
             raise ValueError("%s must be contiguous %s %s" % (n, dt, shp))
+    if lens is not None:
+        check(_lib.load().icka_lstm_fwd_varlen(gates_x.data_ptr(), gates_x.stride(0), w_hh.data_ptr(), y.data_ptr(),
+                                               c_all.data_ptr(), act.data_ptr(), _ptr(hprev), _lstm_lens(lens, B, gates_x),
+                                               B, S, H, int(flags), _stream()), "icka_lstm_fwd_varlen")
+        return
     check(_lib.load().icka_lstm_fwd(gates_x.data_ptr(), gates_x.stride(0), w_hh.data_ptr(), y.data_ptr(),
                                     c_all.data_ptr(), act.data_ptr(), _ptr(hprev), B, S, H, int(flags), _stream()), "icka_lstm_fwd")
 
 
-def lstm_bwd(dy, w_hh_t, act, c_all, dgates, dc_carry, B, S, H, flags=0):
+def lstm_mask_gates(gates_x, lens, B, S, H):
+    """In place: the i and f pre-activations of both directions of an f32 gate buffer [B*S, 8H] := -1e4 at every t >= lens[b]
+    (icka_hip.h: icka_lstm_mask_gates; the fp32 mode's form of the pad mask)."""
+    _dev(gates_x, "gates_x")
+    if gates_x.dtype != F32 or gates_x.stride(1) != 1 or tuple(gates_x.shape) != (B * S, 8 * H):
+        raise ValueError("gates_x must be f32 [B*S, 8H]")
+    check(_lib.load().icka_lstm_mask_gates(gates_x.data_ptr(), gates_x.stride(0), _lstm_lens(lens, B, gates_x), B, S, H,
+                                           _stream()), "icka_lstm_mask_gates")
+    return gates_x
+
+
+def lstm_bwd(dy, w_hh_t, act, c_all, dgates, dc_carry, B, S, H, flags=0, lens=None):
     for n, t, shp, dt in (("dy", dy, (B * S, 2 * H), BF16), ("w_hh_t", w_hh_t, (2 * H, 4 * H), BF16),
                           ("act", act, (B * S, 8 * H), BF16), ("c_all", c_all, (B * S, 2 * H), F32),
                           ("dgates", dgates, (B * S, 8 * H), BF16), ("dc_carry", dc_carry, (2 * B, H), F32)):
         _dev(t, n)
         if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
             raise ValueError("%s must be contiguous %s %s" % (n, dt, shp))
+    if lens is not None:
+        check(_lib.load().icka_lstm_bwd_varlen(dy.data_ptr(), w_hh_t.data_ptr(), act.data_ptr(), c_all.data_ptr(),
+                                               dgates.data_ptr(), dgates.stride(0), dc_carry.data_ptr(),
+                                               _lstm_lens(lens, B, dy), B, S, H, int(flags), _stream()), "icka_lstm_bwd_varlen")
+        return
     check(_lib.load().icka_lstm_bwd(dy.data_ptr(), w_hh_t.data_ptr(), act.data_ptr(), c_all.data_ptr(),
                                     dgates.data_ptr(), dgates.stride(0), dc_carry.data_ptr(), B, S, H, int(flags), _stream()),
           "icka_lstm_bwd")

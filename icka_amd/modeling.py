@@ -1018,7 +1018,10 @@ class MTCCMBertForMMTokenClassificationCRF_gate_1(BertPreTrainedModel):
         B, S = ori_input_ids.shape
         A, _, _, cross, _ = _mner_trunk(self, ori_input_ids, ori_segment_ids, ori_input_mask, added_attention_mask,
                                         visual_embeds_att)
-        x, _ = self.lstm(cross.view(B, S, self.hidden_size))
+        # set_length_aware: packed-sequence semantics, the lengths read from the text mask on the device
+        from .lstm import lengths_of_mask
+        lengths = lengths_of_mask(ori_input_mask) if self.lstm.length_aware else None
+        x, _ = self.lstm(cross.view(B, S, self.hidden_size), lengths=lengths)
         if _is_exact(self):
             em = X.LinearFn.apply(A.anchor, x.reshape(B * S, 2 * self.hidden_size), self.classifier, A, False)
         else:

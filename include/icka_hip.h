@@ -859,6 +859,31 @@ int icka_lstm_bwd(const void* dy, const void* w_hh_t, const void* act, const flo
 #define ICKA_LSTM_PER_STEP 1
 #define ICKA_LSTM_TICKETS 2
 #define ICKA_LSTM_NO_BATCH_SPLIT 4
+/* Variable lengths (pack_padded_sequence semantics; a departure from the reference, whose nn.LSTM call runs over the padding).
+ * The *_varlen entries are icka_lstm_fwd / icka_lstm_bwd plus ``lens``: int32 [B] ON THE DEVICE, read by the kernels (each
+ * reads its rows' lengths once, at its start, clamped to [0, S]); no host value derived from the lengths enters a launch, so
+ * one captured graph serves every batch.  lens == NULL is icka_lstm_fwd / icka_lstm_bwd exactly (which forward here).
+ *   Semantics.  Positions t >= lens[b] are pads.  The state of both directions is zero where a row's live part begins (the
+ *   reverse direction starts at lens[b] - 1), and y, c_all and dgates are EXACTLY zero at every pad: the weight / input gradient
+ *   GEMMs that follow may run over all B*S rows.  act there holds i = f = 0 exactly and finite g, o; hprev is, as everywhere, y
+ *   of the direction's previous step: zero at pads except the forward direction's t = lens[b], which holds h of the last live
+ *   step (finite, and multiplied by a zero dgates row in the dW_hh GEMM).
+ *   Mechanism, bf16 mode: the FORWARD kernels replace the i and f pre-activations they load from gates_x by -1e4 at pads (a
+ *   select at the load; gates_x is not written).  sigmoid gives exactly 0 there, hence c = h = 0, and the backward cell gives
+ *   exactly zero gate gradients from those saved activations whatever dy holds at the pads: the backward needs no mask.
+ *   fp32 mode (exact.hip) has no recurrence kernel of its own to put the select in: icka_lstm_mask_gates writes the same -1e4
+ *   into its f32 gate buffer (layout of gates_x) IN PLACE, at every t >= lens[b], before its per-step loop.
+ *   No step is skipped: every form walks all S positions with the mask, so a call costs what the fixed-length call costs.
+ *   Persistent kernels that stop at the longest live row of the blocks that wait on each other were built and measured: half
+ *   the time at a longest row of 64, but the cost did not follow the steps to within the timing spread (one extra step behind
+ *   the last token and a launch that stores the unwalked positions) -- profiles/NEGATIVE_RESULTS.md, profiles/lstm_varlen.txt.
+ *   icka_lstm_bwd_varlen therefore computes exactly what icka_lstm_bwd computes (``lens`` is accepted for symmetry and for a
+ *   later trimmed form).  The give-up / NaN-poison path and icka_lstm_test_hooks are unchanged. */
+int icka_lstm_fwd_varlen(const float* gates_x, int64_t ldg, const void* w_hh, void* y, float* c_all, void* act, void* hprev,
+                         const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t flags, void* stream);
+int icka_lstm_bwd_varlen(const void* dy, const void* w_hh_t, const void* act, const float* c_all, void* dgates, int64_t ldg,
+                         float* dc_carry, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t flags, void* stream);
+int icka_lstm_mask_gates(float* gates_x, int64_t ldg, const int32_t* lens, int32_t B, int32_t S, int32_t H, void* stream);
 /* The persistent launches wait on words written by other blocks of the same grid, with a bounded spin.  A wait that gives
  * up (a peer block that never became resident, a lost word) raises a sticky error word AND poisons the recurrence: the
  * waiting block continues with NaN operands, so every later step of every block -- y, the loss, every gradient of the

@@ -39,11 +39,16 @@ def main():
     ap.add_argument("--with-encoder", action="store_true",
                     help="also run the frozen ResNet-152 image encoder on 224x224 images inside the step "
                          "(My_cross_attention.py calls it once per batch): end-to-end image+sentence -> loss")
+    ap.add_argument("--length-aware", action="store_true",
+                    help="icka_amd.set_length_aware: packed-sequence semantics in the BiLSTM (zero state at each sentence's end)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(synth.REFERENCE_SEED)
     cfg = BertConfig(30522, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072)
     model = MTCCMBertForMMTokenClassificationCRF_gate_1(cfg, num_labels=13).to(dev).train()
+    if args.length_aware:
+        import icka_amd
+        icka_amd.set_length_aware(model)
     b = synth.synthetic_batch(args.batch, args.seq, args.regions, num_labels=13)
     g = {k: v.to(dev) for k, v in b.items()}
 
@@ -110,6 +115,7 @@ def main():
                       "algorithmic_gflop_per_step": round(3 * fwd * args.batch * 1e-9, 1), "algorithmic_tflops": round(tfl, 1),
                       "frac_of_bf16_mfma_peak": round(tfl / 2500.0, 4),
                       "value": round(1e3 * args.batch / ms, 2), "unit": "samples/s", "ms_per_step": round(ms, 3),
+                      "length_aware": bool(args.length_aware), "longest_sentence": int(b["lengths"].max()),
                       "launch": mode, "loss": round(loss, 5), "n_gpus": 1, "dtype": "bf16", "data": "synthetic",
                       "config": {"workload": "bert-base + %d regions, seq %d, batch %d, train mode"
                                  % (49 if args.with_encoder else args.regions, args.seq, args.batch)},
