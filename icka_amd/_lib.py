@@ -87,6 +87,7 @@ PROTOTYPES = {
     "icka_copy_many": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),
     "icka_build_arch": (C.c_char_p, []),
     "icka_gemm": (c_i32, [C.POINTER(GemmDesc), c_vp]),
+    "icka_gemm_live": (c_i32, [C.POINTER(GemmDesc), c_vp, c_vp]),
     "icka_gemm_grouped": (c_i32, [C.POINTER(GemmDesc), c_i32, c_vp]),
     "icka_gemm_grouped_ex": (c_i32, [C.POINTER(GemmDesc), c_i32, C.POINTER(SlabReduction), c_i32, c_vp]),
     "icka_gemm_grouped_live": (c_i32, [C.POINTER(GemmDesc), c_i32, C.POINTER(SlabReduction), c_i32, C.POINTER(c_vp), c_vp]),

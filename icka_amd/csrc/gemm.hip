@@ -9,6 +9,7 @@
 //   gemm.hip          this file: the host policy (convert, the tune word, the launch ladder, icka_gemm), the general path
 //   gemm_ws.inc       aligned path, 128 x 128 / 96 / 64 tiles: the 256-thread DMA kernels, the 8-wave warp-specialised ones
 //   gemm_w3.inc       12 waves, 256x192 / 256x128 tiles (wide short-K outputs), and the fused QKV + attention twin
+//                     (gemm_w3_body.inc: the statements its plain and its live-rows kernel share)
 //   gemm_fused.inc    the 8-wave kernel with a LayerNorm phase, with BatchNorm statistics, as an implicit 3x3 convolution
 //   gemm_grouped.inc  several problems per launch, 256x128 tiles for the grouped weight gradients, slab reductions
 // Variants of the NT kernels: F16 (IEEE fp16 operands on v_mfma_f32_16x16x32_f16, fp16 / bf16-copy outputs: the "mixed16"
@@ -288,8 +289,11 @@ namespace {
 // "launch this instantiation on this grid, check, return" for the arms of the ladder
 #define LAUNCH_RETURN(KERNEL, GRID, BLOCK) ICKA_LAUNCH_RETURN(KERNEL, GRID, BLOCK, st, g)
 
+// a_live (icka_gemm_live): row-liveness bytes of A, or null.  Two arms of the ladder have a LIVE instance (NN, bf16: the 256x192
+// and the 128x96 ring-of-3 kernels, the input-gradient GEMMs of the encoder backward); every other arm ignores the flags.
 template <bool A_KM, bool B_KM, bool F16 = false>
-int launch(GemmArgs g, bool aligned, hipStream_t st, const Tune& t) {
+int launch(GemmArgs g, bool aligned, hipStream_t st, const Tune& t, const uint8_t* a_live = nullptr) {
+    constexpr bool LIVE_OK = !A_KM && B_KM && !F16;
     const int nb = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
     if constexpr (!A_KM && !B_KM) {
         if (!aligned && g.n64ok && t.ws)   // 64-channel convolutions of the ResNet stem / layer1: 128x64 tiles
@@ -324,6 +328,13 @@ int launch(GemmArgs g, bool aligned, hipStream_t st, const Tune& t) {
                     if (t.w3 && g.M % 256 == 0 && g.N % 192 == 0 && g.K <= 1024 && g.K1 == 0 && nb3 % 8 == 0 &&
                         nb3 >= 128 && 4 * nb3 >= 3 * 256 * rounds3 && g.ksplit == 1) {
                         w3_set_grid(g, 192, t.w3grid);
+                        if constexpr (LIVE_OK) {
+                            if (a_live) {
+                                hipLaunchKernelGGL(gemm_w3_live_kernel, dim3(nb3), dim3(768), 0, st, g, a_live);
+                                ICKA_CHECK_LAUNCH();
+                                return 0;
+                            }
+                        }
                         LAUNCH_RETURN((gemm_w3_kernel<B_KM, F16>), nb3, 768);
                     }
                     // 256x128 tiles (the same kernel, 64-column halves) where 128x128 tiles would take exactly two rounds of
@@ -348,6 +359,11 @@ int launch(GemmArgs g, bool aligned, hipStream_t st, const Tune& t) {
                             LAUNCH_RETURN((gemm_ws2_kernel<A_KM, B_KM, 96, F16>), nb96, 512);
                         else if (t.nbuf == 4 && !F16) LAUNCH_RETURN((gemm_ws_kernel<A_KM, B_KM, 4, 0, 96>), nb96, 512);
                         else if (t.nbuf == 5 && !F16) LAUNCH_RETURN((gemm_ws_kernel<A_KM, B_KM, 5, 0, 96>), nb96, 512);
+                        else if (LIVE_OK && a_live) {
+                            if constexpr (LIVE_OK) hipLaunchKernelGGL(gemm_ws_live_kernel<96>, dim3(nb96), dim3(512), 0, st, g, a_live);
+                            ICKA_CHECK_LAUNCH();
+                            return 0;
+                        }
                         else LAUNCH_RETURN((gemm_ws_kernel<A_KM, B_KM, 3, 0, 96, F16>), nb96, 512);
                     }
                 }
@@ -408,4 +424,19 @@ extern "C" int icka_gemm(const icka_gemm_desc* d, void* stream) {
         case ICKA_GEMM_NN: return launch<false, true>(g, aligned, st, t);
         default: return launch<true, true>(g, aligned, st, t);
     }
+}
+
+// icka_gemm with row-liveness flags of the A operand (include/icka_hip.h).  The flags are a permission: a launch whose kernel has
+// no LIVE instance, or a null pointer, is exactly icka_gemm.
+extern "C" int icka_gemm_live(const icka_gemm_desc* d, const uint8_t* a_row_live, void* stream) {
+    if (!a_row_live) return icka_gemm(d, stream);
+    if (reinterpret_cast<uintptr_t>(a_row_live) & 15) return ICKA_E_ALIGN;
+    GemmArgs g;
+    Tune t;
+    bool aligned = false;
+    const int rc = convert(d, g, aligned, t);
+    if (rc) return rc;
+    if (d->op != ICKA_GEMM_NN && d->op != ICKA_GEMM_NT) return ICKA_E_ARG;   // (flags are per ROW of a row-major A)
+    if (d->op != ICKA_GEMM_NN || g.f16 || g.K1 != 0 || !aligned || !t.ws || t.abl) return icka_gemm(d, stream);
+    return launch<false, true>(g, aligned, (hipStream_t)stream, t, a_row_live);
 }

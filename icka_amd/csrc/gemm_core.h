@@ -377,6 +377,34 @@ __device__ __forceinline__ void dma_issue_at(const bf16_t* const (&ptr)[4], int6
     dma_issue(q, 0, lds_base);
 }
 
+// ---- live A rows (icka_gemm_live: the LIVE instances of gemm_ws_body and of the 12-wave kernel).  a_live[t] == 0 promises that
+// row t of A is all zero.  A loader wave's 1-KiB piece is 8 tile rows; a piece whose 8 bytes are all 0 is staged from this
+// never-written line of zeros instead of from A (all 64 lanes read inside its 128 bytes, and the pointer does not advance with k):
+// LDS receives the same zeros, the DMA sequence and every counted wait stay what they are, and the dead rows' bytes never leave L2.
+__device__ __attribute__((aligned(128))) uint32_t g_zero_line[32];
+
+// the 8 flag bytes of piece wave + 4 j of the 128-row A image at row0 (row0 % 128 == 0, a_live 16-byte aligned), j = 0 .. 3
+__device__ __forceinline__ void live_request(uint64_t (&fl)[4], const uint8_t* __restrict__ a_live, int row0, int wave) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) fl[j] = *reinterpret_cast<const uint64_t*>(a_live + row0 + 8 * (wave + 4 * j));
+}
+// redirect the dead pieces of dma_init's pointers to the zero line; st[j] = the per-k-tile stride of piece j (0 when dead)
+__device__ __forceinline__ void live_select(const bf16_t* (&ptr)[4], int64_t (&st)[4], const uint64_t (&fl)[4], int64_t stride, int lane) {
+    const bf16_t* z = reinterpret_cast<const bf16_t*>(g_zero_line) + 8 * (lane & 7);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool dead = fl[j] == 0;
+        ptr[j] = dead ? z : ptr[j];
+        st[j] = dead ? 0 : stride;
+    }
+}
+// dma_issue with a stride per piece
+__device__ __forceinline__ void dma_issue_live(const bf16_t* (&ptr)[4], const int64_t (&st)[4], uint32_t lds_base) {
+    dma_issue(ptr, 0, lds_base);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ptr[j] += st[j];
+}
+
 // f32 C tile in LDS: [128 rows][32 chunks of 4 floats], chunk index XORed with row&31
 __device__ __forceinline__ uint32_t off_c(int row, int ch) { return row * 512 + ((ch ^ (row & 31)) << 4); }
 // same for a 192-column f32 tile (48 chunks of 16 B per row; the XOR stays inside each group of 16 chunks)

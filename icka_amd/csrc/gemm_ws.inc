@@ -4,6 +4,7 @@
 //   gemm_dma_kernel        256 threads, LDS-DMA staging (predecessor of the warp-specialised kernels)
 //   gemm_ws_kernel         512 threads: 4 loader waves (LDS-DMA) + 4 compute waves, ring of 3 .. 5 k-tiles, 128x128, 128x96 or
 //                          128x64 output tiles, LDS-staged or direct (f32) epilogue; bf16 or (NT) fp16 operands
+//   gemm_ws_live_kernel    the NN ring-of-3 instance with row-liveness flags of A (icka_gemm_live)
 //   gemm_ws2_kernel        same with a ring of 2 and two co-resident blocks per CU (short-K, many-tile grids)
 // Which of them a call gets is decided by the launch ladder of gemm.hip.  A source fragment of gemm.hip, included once there.
 #include "gemm_core.h"
@@ -228,10 +229,12 @@ __device__ __forceinline__ bool g_direct_epilogue(const GemmArgs& g) {
 // waves -- the kernel then hands the stripe's rows over to its LayerNorm phase inside the same launch.
 // STATS (gemm_ws_bn_stats_kernel): the raw output tile (no bias / activation) is stored as usual, and bn_stats_tile writes
 // the train-mode BatchNorm partials of its columns from the f32 tile in LDS to stats_part.
+// LIVE (gemm_ws_live_kernel): a_live holds one byte per row of A, 0 = the row is all zero; the loader waves stage the 8-row
+// pieces without a live row from the zero line of gemm_core.h.  Everything else, the compute waves included, is the plain body.
 template <bool A_KM, bool B_KM, int NBUF, int ABL = 0, int DIST = 2, int BNT = 128, bool F16 = false, bool CONV = false, bool LNF = false,
-          bool STATS = false>
+          bool STATS = false, bool LIVE = false>
 __device__ __forceinline__ void gemm_ws_body(const GemmArgs& g, char* smem, const int bid, const int nb, float* stats_part = nullptr,
-                                             int stats_rows = 0) {
+                                             int stats_rows = 0, const uint8_t* a_live = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(LDS_PTR(char, smem)));
@@ -267,6 +270,14 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& g, char* smem, cons
         const int k1t = g.K1 > 0 ? g.K1 / BK : -1;
         const bf16_t* pa[4];
         const bf16_t* pb[4];
+        // LIVE: the flags are requested first; the B pieces of k-tile 0 go out while they are in flight (within a k-tile the order
+        // of the pieces is free: the counted waits are in whole tiles)
+        uint64_t fl[4] = {0, 0, 0, 0};
+        int64_t sal[4] = {0, 0, 0, 0};
+        if constexpr (LIVE) {
+            static_assert(!A_KM && !CONV && ABL == 0, "live A rows: a k-contiguous A operand");
+            live_request(fl, a_live, m0, lw);
+        }
         // CONV: the A tile is gathered from the NHWC activation.  Per piece (8 tile rows) this lane serves one output pixel:
         // the pointer to its centre input pixel (+ this lane's 16-byte chunk) and a 9-bit mask of the taps that lie inside
         // the image; a k-tile is 64 channels of ONE tap (cvC % 64 == 0), so its source is centre + a wave-uniform offset,
@@ -301,8 +312,18 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& g, char* smem, cons
         }
         dma_init<B_KM, BNT>(pb, g.B, g.ldb, n0, lw, lane);
         int64_t sa = CONV ? 0 : (A_KM ? (int64_t)BK * g.lda : BK), sb = B_KM ? (int64_t)BK * g.ldb : BK;
+        if constexpr (LIVE) {   // (the host sends no two-segment reduction here: k1t stays -1)
+            if (nk > 0) dma_issue<NJB>(pb, sb, lds0 + TILE_BYTES + lw * 1024);
+            live_select(pa, sal, fl, sa, lane);
+            if (nk > 0) dma_issue_live(pa, sal, lds0 + lw * 1024);
+        }
 #define ICKA_WS_STAGE(KT, BUF)                                          \
     do {                                                                \
+        if constexpr (LIVE) {                                           \
+            dma_issue_live(pa, sal, lds0 + (BUF) + lw * 1024);          \
+            dma_issue<NJB>(pb, sb, lds0 + (BUF) + TILE_BYTES + lw * 1024); \
+            break;                                                      \
+        }                                                               \
         if ((KT) == k1t) {                                              \
             dma_init<A_KM>(pa, g.A2, g.lda2, m0, lw, lane);             \
             dma_init<B_KM, BNT>(pb, g.B2, g.ldb2, n0, lw, lane);        \
@@ -321,7 +342,7 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& g, char* smem, cons
         }                                                               \
     } while (0)
 #pragma unroll
-        for (int t = 0; t < NBUF - 1; ++t)
+        for (int t = LIVE ? 1 : 0; t < NBUF - 1; ++t)
             if (t < nk) ICKA_WS_STAGE(t, t * 2 * TILE_BYTES);
         int cur = 0;
         ICKA_STAMP(unsigned long long seg[4] = {0, 0, 0, 0}, tA, tB;
@@ -573,6 +594,14 @@ __global__ __launch_bounds__(512, 4) void gemm_ws2_kernel(const GemmArgs gp) {
     const GemmArgs g = gp;
     __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_BYTES];
     gemm_ws_body<A_KM, B_KM, 2, 0, 1, BNT, F16>(g, smem, blockIdx.x, gridDim.x);
+}
+
+// the NN kernel with row-liveness flags of A (icka_gemm_live; ring of 3 as the plain launch of these shapes)
+template <int BNT>
+__global__ __launch_bounds__(512) void gemm_ws_live_kernel(const GemmArgs gp, const uint8_t* a_live) {
+    const GemmArgs g = gp;
+    __shared__ __attribute__((aligned(16))) char smem[3 * 2 * TILE_BYTES];
+    gemm_ws_body<false, true, 3, 0, 2, BNT, false, false, false, false, true>(g, smem, blockIdx.x, gridDim.x, nullptr, 0, a_live);
 }
 
 template <bool A_KM, bool B_KM, int NBUF, int ABL>

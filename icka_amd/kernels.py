@@ -83,7 +83,9 @@ def profile_gemm(enable: bool, reps: int = 5):
 
     def replay(which):
         for kind, payload, n, _keep in which:
-            if kind == 0:
+            if kind == 0 and isinstance(n, torch.Tensor):
+                check(lib.icka_gemm_live(C.byref(payload), n.data_ptr(), _stream()), "icka_gemm_live")
+            elif kind == 0:
                 check(lib.icka_gemm(C.byref(payload), _stream()), "icka_gemm")
             elif kind == 1:
                 check(lib.icka_gemm_grouped(payload, n, _stream()), "icka_gemm_grouped")
@@ -254,13 +256,24 @@ def gemm_tune(*, ring: Optional[int] = None, tile_n: Optional[int] = None, wide_
     return t
 
 
-def gemm(op: int, A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, **kw) -> torch.Tensor:
-    """out[M,N] = epilogue(alpha * op(A,B) [+ op(A2,B2)] + bias) + beta*out.   op: GEMM_NT / GEMM_NN / GEMM_TN."""
+def gemm(op: int, A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, *, a_live: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
+    """out[M,N] = epilogue(alpha * op(A,B) [+ op(A2,B2)] + bias) + beta*out.   op: GEMM_NT / GEMM_NN / GEMM_TN.
+    ``a_live`` (op NN / NT): uint8 [M] row-liveness flags of A (icka_gemm_live): byte t may be 0 only if row t of A is all zero;
+    the launches that have a LIVE instance then do not fetch the 8-row pieces of A without a live row.  Bitwise the plain call."""
     lib = _lib.load()
     d = gemm_desc(op, A, B, out, **kw)
-    if _PROF is not None:
-        _PROF.append((0, d, 1, [d]))
-    check(lib.icka_gemm(C.byref(d), _stream()), "icka_gemm")
+    if a_live is not None:
+        _dev(a_live, "a_live")
+        if op not in (GEMM_NN, GEMM_NT):
+            raise ValueError("gemm: a_live flags the rows of a row-major A (op NN or NT)")
+        if a_live.dtype != torch.uint8 or not a_live.is_contiguous() or a_live.numel() != d.M:
+            raise ValueError("gemm: a_live must be a contiguous uint8 [M] tensor")
+    if _PROF is not None:   # (a live launch is recorded, and replayed, with its flags: same descriptor, same FLOPs)
+        _PROF.append((0, d, a_live if a_live is not None else 1, [d]))
+    if a_live is not None:
+        check(lib.icka_gemm_live(C.byref(d), a_live.data_ptr(), _stream()), "icka_gemm_live")
+    else:
+        check(lib.icka_gemm(C.byref(d), _stream()), "icka_gemm")
     return out
 
 

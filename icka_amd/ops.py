@@ -42,6 +42,10 @@ FUSE_QKV_ATTN_MIN_ROWS = 3072
 # liveness byte per row and the 12-wave weight-gradient launch skips the 64-token k-tiles without a live row (padding, when the
 # caller's loss leaves it without gradient).  Bitwise the full reduction.  "0" reduces over every row (same-box A/B: tools/ab_env.sh).
 WGRAD_LIVE = _os.environ.get("ICKA_WGRAD_LIVE", "1") != "0"
+# The same liveness bytes go to the four input-gradient GEMMs of the layer, whose A operand (dfo, dz, dao, dqkv) has an all-zero row
+# wherever the byte is 0: their loader waves then stage the 8-row pieces without a live row from a line of zeros instead of fetching
+# them (icka_gemm_live).  Bitwise the plain launches.  Needs the flags of WGRAD_LIVE; "0" keeps the plain launches.
+DGRAD_LIVE = _os.environ.get("ICKA_DGRAD_LIVE", "1") != "0"
 
 
 def _keepbits_on(Sq: int, Skv: int) -> bool:
@@ -311,7 +315,8 @@ def _attn_core_fwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
 def _attn_core_bwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, saved, ctx, dctx, dres, need_dkv_src: bool,
                    k_live=None):
     """Returns (dx, dkv_src); ``dres`` (optional) is added to dx in the last GEMM's epilogue (residual fan-in).
-    ``k_live`` (self-attention only): row-liveness flags of dqkv (row_live_kv of the block's LayerNorm backward)."""
+    ``k_live`` (self-attention only): row-liveness flags of dqkv (row_live_kv of the block's LayerNorm backward), for its weight
+    gradient and (DGRAD_LIVE) its input gradient."""
     qkv, kvbuf, lse, seed_a, kb = saved
     M, H = x.shape
     generic = isinstance(lse, tuple)       # head size != 64: the saved f32 operands / probabilities of _attn_generic_fwd
@@ -332,7 +337,7 @@ def _attn_core_bwd(A: ParamArena, sa, x, kv_src, add_mask, d: Dims, Skv: int, sa
         bg = (sa.query.bias, sa.key.bias, sa.value.bias)
         _wgrad(A, dqkv, x, A.g_cat(wg), A.grad_beta(wg), bias=bg, k_live=k_live)
         dx = _empty(x, M, H)
-        K.gemm(K.GEMM_NN, dqkv, A.w_cat(wg), dx, **epi)
+        K.gemm(K.GEMM_NN, dqkv, A.w_cat(wg), dx, a_live=k_live if DGRAD_LIVE else None, **epi)
         return dx, None
     dq = _empty(x, M, H)
     dkv = _empty(x, kv_src.shape[0], 2 * H)
@@ -427,10 +432,11 @@ def _inter_bwd(A: ParamArena, inter, x, dz, dres, k_live=None):
     """dz = gradient of the pre-activation.  Returns dx (+ dres when given)."""
     _wgrad(A, dz, x, A.g(inter.dense.weight), A.grad_beta(inter.dense.weight), bias=inter.dense.bias, k_live=k_live)
     dx = _empty(x, x.shape[0], x.shape[1])
+    a_live = k_live if DGRAD_LIVE else None
     if dres is not None:
-        K.gemm(K.GEMM_NN, dz, A.w(inter.dense.weight), dx, epilogue=K.EPI_ADD, aux=dres)
+        K.gemm(K.GEMM_NN, dz, A.w(inter.dense.weight), dx, epilogue=K.EPI_ADD, aux=dres, a_live=a_live)
     else:
-        K.gemm(K.GEMM_NN, dz, A.w(inter.dense.weight), dx)
+        K.gemm(K.GEMM_NN, dz, A.w(inter.dense.weight), dx, a_live=a_live)
     return dx
 
 
@@ -455,7 +461,7 @@ def _attn_block_bwd(A: ParamArena, att, x, kv_src, add_mask, d: Dims, Skv: int, 
     dao, dres, flags = _dense_norm_bwd(A, "ln_attn", att.output, ctx, d, s_out, dy, dy2, live=live,
                                        add_mask=add_mask if live else None)
     dctx = _empty(x, x.shape[0], x.shape[1])
-    K.gemm(K.GEMM_NN, dao, A.w(att.output.dense.weight), dctx)
+    K.gemm(K.GEMM_NN, dao, A.w(att.output.dense.weight), dctx, a_live=flags[0] if flags and DGRAD_LIVE else None)
     return _attn_core_bwd(A, att.self, x, kv_src, add_mask, d, Skv, s_core, ctx, dctx, dres, need_dkv_src,
                           k_live=flags[1] if flags else None)
 
@@ -473,7 +479,8 @@ def _ffn_block_bwd(A: ParamArena, layer, x, d: Dims, saved, dy, dy2=None, live=F
     z, g, s_out = saved
     dfo, dres, flags = _dense_norm_bwd(A, "ln_ffn", layer.output, g, d, s_out, dy, dy2, live=live)
     dz = _empty(x, z.shape[0], z.shape[1])
-    K.gemm(K.GEMM_NN, dfo, A.w(layer.output.dense.weight), dz, epilogue=K.EPI_DGELU, aux=z)
+    K.gemm(K.GEMM_NN, dfo, A.w(layer.output.dense.weight), dz, epilogue=K.EPI_DGELU, aux=z,
+           a_live=flags[0] if flags and DGRAD_LIVE else None)
     return _inter_bwd(A, layer.intermediate, x, dz, dres, k_live=flags[0] if flags else None)
 
 

@@ -140,6 +140,14 @@ typedef struct icka_gemm_desc {
 #define ICKA_TUNE_BIG_TILES(v) ((uint64_t)((v) + 1) << 24)
 #define ICKA_TUNE_ABLATION(m) ((uint64_t)(m) << 28)
 int icka_gemm(const icka_gemm_desc* d, void* stream);
+/* icka_gemm with row-liveness flags of the A operand (op NN or NT: A is [M, K] row-major): a_row_live is NULL or M bytes,
+ * 16-byte aligned; byte t may be 0 only if row t of A is all zero (icka_ln_bwd_slabs_live writes such bytes for the gradient
+ * rows of a BERT layer).  The flags are a permission, never an obligation: the NN launches on 256x192 tiles (12-wave kernel)
+ * and on 128x96 tiles (8-wave kernel, ring of 3) -- the input-gradient GEMMs of the encoder backward -- stage the 8-row pieces of
+ * A that have no live row from a line of zeros instead of fetching them; every other launch, and a NULL pointer, is exactly
+ * icka_gemm.  The staged tile holds the same zeros either way, so the result is bitwise that of icka_gemm for any B (non-finite
+ * values included); the epilogue and its aux reads run for every row. */
+int icka_gemm_live(const icka_gemm_desc* d, const uint8_t* a_row_live, void* stream);
 /* n independent GEMMs; consecutive fast-path problems of one layout are packed (up to 4) into ONE launch so that
  * several partially-filling grids (the weight-gradient GEMMs of a layer) fill the chip together. */
 int icka_gemm_grouped(const icka_gemm_desc* descs, int32_t n, void* stream);
