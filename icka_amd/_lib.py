@@ -80,6 +80,20 @@ class OptimState(C.Structure):
 
 OptimState.HOST_LO, OptimState.HOST_HI = OptimState.kind.offset, OptimState.lr.offset
 
+AVERAGE_EMA, AVERAGE_SWA = 0, 1
+
+
+class AverageState(C.Structure):
+    """Mirror of ``icka_average_state`` (include/icka_hip.h): the device block of the averaged weights.  Bytes [0, HOST_LO)
+    are written by icka_optim_average_prepare (and ``n`` by the host on resume), [HOST_LO, size) by the host."""
+    _fields_ = [
+        ("n", c_i64), ("decay_now", c_f32), ("apply", c_i32), ("kind", c_i32), ("warmup", c_i32), ("decay", C.c_double),
+        ("start", c_i64), ("every", c_i64),
+    ]
+
+
+AverageState.HOST_LO = AverageState.kind.offset
+
 
 # name -> (restype, argtypes); must list every function declared in include/icka_hip.h
 PROTOTYPES = {
@@ -252,6 +266,10 @@ PROTOTYPES = {
                                  c_i32, c_vp]),
     "icka_optim_prepare": (c_i32, [c_vp, c_i32, c_f32, c_i32, c_vp, c_vp]),
     "icka_optim_adamw_dev": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "icka_optim_average": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
+    "icka_optim_average_prepare": (c_i32, [c_vp, c_vp, c_vp]),
+    "icka_optim_average_dev": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "icka_optim_swap": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     # ---- fp32 "exact" mode (csrc/exact.hip)
     "icka_x_gemm": (c_i32, [C.POINTER(XGemmDesc), c_vp]),
     "icka_x_ln_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_u64,

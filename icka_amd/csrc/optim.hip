@@ -14,6 +14,12 @@
 //   icka_optim_prepare    (in place of icka_optim_clip) norm, non-finite test, clip coefficient, this update's lr / bias
 //                         corrections per group, t += 1 -- or, for a non-finite norm, the skip word
 //   icka_optim_adamw_dev  all groups in one launch, values from the block; returns at once when the skip word is set
+// An averaged copy of the weights (EMA / SWA; outside the reference, off by default) is one more f32 buffer of the same layout:
+//   icka_optim_average          avg <- avg + (1 - d) (p - avg) over a chunk table of every parameter  (12 B per parameter)
+//   icka_optim_average_prepare  (capturable form) one thread behind icka_optim_prepare: is this update averaged, its decay,
+//                               n += 1, in a second device block (icka_average_state); icka_optim_average_dev reads it
+//   icka_optim_swap             p <-> avg in place, with the 16-bit shadows of the new p: evaluating the averaged weights keeps
+//                               every address a captured graph holds
 #include "common.h"
 
 namespace {
@@ -218,6 +224,100 @@ __global__ __launch_bounds__(256) void optim_adamw_dev_kernel(const AdamDevArgs 
     }
 }
 
+// ---- averaged weights (icka_average_state, include/icka_hip.h): an EMA / SWA copy of the parameters kept beside the update
+using AvgState = icka_average_state;
+
+// One thread, behind optim_prepare_kernel: whether the update that prepare just admitted (number st->t) is averaged, and with
+// which decay.  A refused or dry update (skip) is never averaged and never counted.
+__global__ void optim_average_prepare_kernel(AvgState* __restrict__ av, const OptState* __restrict__ st) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (st->skip) {
+        av->apply = 0;
+        return;
+    }
+    const int64_t t = st->t, start = av->start, every = av->every > 0 ? av->every : 1;
+    if (!(t > start && (t - start - 1) % every == 0)) {
+        av->apply = 0;
+        return;
+    }
+    const int64_t n = av->n;
+    double d;
+    if (n == 0) {
+        d = 0.0;
+    } else if (av->kind == ICKA_AVERAGE_SWA) {
+        d = (double)n / (double)(n + 1);
+    } else {
+        d = av->decay;
+        if (av->warmup) {
+            const double w = (double)(1 + n) / (double)(10 + n);
+            d = w < d ? w : d;
+        }
+    }
+    av->decay_now = (float)d;
+    av->n = n + 1;
+    av->apply = 1;
+}
+
+// avg <- avg + (1 - decay) * (p - avg) over the chunks of the table (pairs, as optim_adamw_kernel's).  av != NULL: the decay
+// and the apply word come from the block the prepare launch in front wrote (one compilation serves both forms: they agree
+// bit for bit).  decay == 0 stores p itself: avg + (p - avg) is not p in floating point.
+__global__ __launch_bounds__(256) void optim_average_kernel(const float* __restrict__ p, float* __restrict__ avg,
+                                                            const int64_t* __restrict__ table, const AvgState* __restrict__ av,
+                                                            float decay) {
+    if (av) {
+        if (!av->apply) return;
+        decay = av->decay_now;
+    }
+    const int64_t lo = table[2 * blockIdx.x], len = table[2 * blockIdx.x + 1];
+    const float w = 1.f - decay;
+    const bool copy = decay == 0.f;
+    for (int64_t c = threadIdx.x * 8; c < len; c += 256 * 8) {
+        const int64_t i = lo + c;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i + 4 * h);
+            f32x4 o = pv;
+            if (!copy) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(avg + i + 4 * h);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = a[e] + w * (pv[e] - a[e]);
+            }
+            *reinterpret_cast<f32x4*>(avg + i + 4 * h) = o;
+        }
+    }
+}
+
+// p <-> avg over the chunks of the table, and the 16-bit shadows of the new p as optim_adamw_kernel stores them
+__global__ __launch_bounds__(256) void optim_swap_kernel(float* __restrict__ p, float* __restrict__ avg, bf16_t* __restrict__ shadow,
+                                                         _Float16* __restrict__ shadow16, const int64_t* __restrict__ table) {
+    const int64_t lo = table[2 * blockIdx.x], len = table[2 * blockIdx.x + 1];
+    for (int64_t c = threadIdx.x * 8; c < len; c += 256 * 8) {
+        const int64_t i = lo + c;
+        float np[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i + 4 * h);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(avg + i + 4 * h);
+            *reinterpret_cast<f32x4*>(p + i + 4 * h) = a;
+            *reinterpret_cast<f32x4*>(avg + i + 4 * h) = pv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) np[4 * h + e] = a[e];
+        }
+        if (shadow) {
+            bf16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = f2bf(np[e]);
+            *reinterpret_cast<u32x4*>(shadow + i) = as_u32x4(o);
+        }
+        if (shadow16) {
+            f16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (_Float16)fminf(fmaxf(np[e], -65504.f), 65504.f);
+            *reinterpret_cast<f16x8*>(shadow16 + i) = o;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int64_t icka_optim_chunk_elems(void) { return OPT_CHUNK; }
@@ -279,6 +379,51 @@ extern "C" int icka_optim_adamw_dev(float* params, const float* grads, float* ex
     a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.shadow = (bf16_t*)shadow_bf16; a.shadow16 = (_Float16*)shadow_f16;
     a.table = table3_dev; a.st = (const OptState*)state;
     hipLaunchKernelGGL(optim_adamw_dev_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, a);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int icka_optim_average(const float* params, float* avg, const int64_t* table_dev, int32_t n_chunks, float decay,
+                                  void* stream) {
+    if (!params || !avg || !table_dev || params == avg) return ICKA_E_ARG;
+    if (n_chunks <= 0 || !(decay >= 0.f && decay < 1.f)) return ICKA_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(avg)) & 15) return ICKA_E_ALIGN;
+    hipLaunchKernelGGL(optim_average_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, params, avg, table_dev,
+                       (const AvgState*)nullptr, decay);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int icka_optim_average_prepare(void* average_state, const void* optim_state, void* stream) {
+    if (!average_state || !optim_state) return ICKA_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(average_state) | reinterpret_cast<uintptr_t>(optim_state)) & 7) return ICKA_E_ALIGN;
+    hipLaunchKernelGGL(optim_average_prepare_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (AvgState*)average_state,
+                       (const OptState*)optim_state);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int icka_optim_average_dev(const float* params, float* avg, const int64_t* table_dev, int32_t n_chunks,
+                                      const void* average_state, void* stream) {
+    if (!params || !avg || !table_dev || !average_state || params == avg) return ICKA_E_ARG;
+    if (n_chunks <= 0) return ICKA_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(avg)) & 15) return ICKA_E_ALIGN;
+    if (reinterpret_cast<uintptr_t>(average_state) & 7) return ICKA_E_ALIGN;
+    hipLaunchKernelGGL(optim_average_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, params, avg, table_dev,
+                       (const AvgState*)average_state, 0.f);
+    ICKA_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int icka_optim_swap(float* params, float* avg, void* shadow_bf16, void* shadow_f16, const int64_t* table_dev,
+                               int32_t n_chunks, void* stream) {
+    if (!params || !avg || !table_dev || params == avg) return ICKA_E_ARG;
+    if (n_chunks <= 0) return ICKA_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(avg) | reinterpret_cast<uintptr_t>(shadow_bf16) |
+         reinterpret_cast<uintptr_t>(shadow_f16)) & 15)
+        return ICKA_E_ALIGN;
+    hipLaunchKernelGGL(optim_swap_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, params, avg, (bf16_t*)shadow_bf16,
+                       (_Float16*)shadow_f16, table_dev);
     ICKA_CHECK_LAUNCH();
     return 0;
 }

@@ -1791,6 +1791,85 @@ def optim_adamw_dev(flat, gflat, m, v, shadow, shadow16, table3: torch.Tensor, s
           "icka_optim_adamw_dev")
 
 
+# ------------------------------------------------------------------------------------------------- averaged weights (EMA / SWA)
+def average_state_new(device) -> torch.Tensor:
+    """A zeroed ``icka_average_state`` block (include/icka_hip.h; mirror: _lib.AverageState) as a uint8 device tensor."""
+    n = C.sizeof(_lib.AverageState)
+    return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device).view(torch.uint8)[:n]
+
+
+def average_state_write(state: torch.Tensor, host: "_lib.AverageState", lo: int, hi: int) -> None:
+    """Upload bytes [lo, hi) of ``host`` into the device block (outside a capture: a host-to-device copy)."""
+    state[lo:hi].copy_(torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8)[lo:hi])
+
+
+def average_state_read(state: torch.Tensor) -> "_lib.AverageState":
+    """The device block as a host structure (one device-to-host copy: synchronises)."""
+    return _lib.AverageState.from_buffer_copy(bytes(state.cpu().tolist()))
+
+
+def _average_operands(what: str, flat, avg, table) -> None:
+    for n, t in (("params", flat), ("avg", avg)):
+        _dev(t, n)
+        if t.dtype != F32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != flat.numel():
+            raise TypeError("%s: %s must be a contiguous 1-D f32 tensor of the parameters' length" % (what, n))
+    if flat.data_ptr() == avg.data_ptr():
+        raise ValueError("%s: params and avg are the same buffer" % what)
+    _dev(table, "table")
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 2 or not table.is_contiguous():
+        raise TypeError("%s: the chunk table is a contiguous int64 [n, 2] tensor (dp_chunk_table)" % what)
+
+
+def _state_operand(what: str, state: torch.Tensor, mirror) -> None:
+    _dev(state, "state")
+    if state.dtype != torch.uint8 or state.numel() != C.sizeof(mirror) or not state.is_contiguous():
+        raise TypeError("%s: the state block is a uint8 tensor of %d bytes" % (what, C.sizeof(mirror)))
+
+
+def optim_average(flat: torch.Tensor, avg: torch.Tensor, table: torch.Tensor, decay: float) -> None:
+    """avg <- avg + (1 - decay) * (flat - avg) over the chunks of ``table`` (dp_chunk_table); decay == 0 copies."""
+    _average_operands("optim_average", flat, avg, table)
+    if not 0.0 <= float(decay) < 1.0:
+        raise ValueError("optim_average: decay in [0, 1), got %r" % (decay,))
+    if table.shape[0] == 0:
+        return
+    check(_lib.load().icka_optim_average(flat.data_ptr(), avg.data_ptr(), table.data_ptr(), table.shape[0], float(decay),
+                                         _stream()), "icka_optim_average")
+
+
+def optim_average_prepare(average_state: torch.Tensor, optim_state: torch.Tensor) -> None:
+    """Behind optim_prepare: whether the update it admitted is averaged, and this update's decay, into the average block."""
+    _state_operand("optim_average_prepare", average_state, _lib.AverageState)
+    _state_operand("optim_average_prepare", optim_state, _lib.OptimState)
+    check(_lib.load().icka_optim_average_prepare(average_state.data_ptr(), optim_state.data_ptr(), _stream()),
+          "icka_optim_average_prepare")
+
+
+def optim_average_dev(flat: torch.Tensor, avg: torch.Tensor, table: torch.Tensor, average_state: torch.Tensor) -> None:
+    """optim_average with the decay of the average block (nothing is touched when its apply word is 0)."""
+    _average_operands("optim_average_dev", flat, avg, table)
+    _state_operand("optim_average_dev", average_state, _lib.AverageState)
+    if table.shape[0] == 0:
+        return
+    check(_lib.load().icka_optim_average_dev(flat.data_ptr(), avg.data_ptr(), table.data_ptr(), table.shape[0],
+                                             average_state.data_ptr(), _stream()), "icka_optim_average_dev")
+
+
+def optim_swap(flat: torch.Tensor, avg: torch.Tensor, shadow: Optional[torch.Tensor], shadow16: Optional[torch.Tensor],
+               table: torch.Tensor) -> None:
+    """Exchange flat and avg over the chunks of ``table`` and write the 16-bit shadows of the new flat (either may be None)."""
+    _average_operands("optim_swap", flat, avg, table)
+    for n, t, dt in (("shadow", shadow, BF16), ("shadow16", shadow16, F16)):
+        if t is not None:
+            _dev(t, n)
+            if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != flat.numel():
+                raise TypeError("optim_swap: %s must be a contiguous 1-D %s tensor of the parameters' length" % (n, dt))
+    if table.shape[0] == 0:
+        return
+    check(_lib.load().icka_optim_swap(flat.data_ptr(), avg.data_ptr(), _ptr(shadow), _ptr(shadow16), table.data_ptr(),
+                                      table.shape[0], _stream()), "icka_optim_swap")
+
+
 # ------------------------------------------------------------------------------------------------- per-sample gates
 def sample_gate_fwd(a, c, gate, mode, out, B, S):
     _mat(a, "a"); _mat(out, "out")

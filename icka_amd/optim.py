@@ -30,9 +30,25 @@ BASE rate.  DO NOT attach a torch LR scheduler in this mode: it would rewrite th
 only outside a capture), compounding with the device schedule in eager steps and doing nothing at all in replayed ones.
 With ``skip_nonfinite=True`` (default) a NaN / inf gradient norm refuses the update on the device: parameters, moments and
 shadows stay as they are, t does not advance, ``skipped_steps()`` counts it.
+
+``ArenaAdamW(..., average="ema" | "swa")``: an averaged copy of the weights, kept beside the update.  One more f32 buffer of the
+arena's layout holds it; behind every update that ``average_start`` / ``average_every`` select, ONE launch over a chunk table of
+every parameter of the groups moves it (``avg += (1 - d) * (p - avg)``; d = ``average_decay_at``: 0 for the first averaged
+update, ``n / (n + 1)`` for SWA, ``min(decay, (1 + n) / (10 + n))`` for an EMA with warm-up).  In capturable mode the count n
+and the decay live in a second device block (icka_average_state) written by a one-thread launch behind icka_optim_prepare, so
+the averaging is captured with ``step()`` and a refused (non-finite) or dry update is neither averaged nor counted.
+``averaged_weights()`` exchanges parameters and average IN PLACE (icka_optim_swap, which also writes the 16-bit shadows of the
+weights it swaps in), so the model, its ``state_dict()`` and every graph captured earlier -- a ``GraphedModule`` dev pass --
+run on the averaged weights inside the context without a re-cast and without a re-capture; ``step()`` and
+``TrainStep.__call__`` refuse while they are swapped in.  Until the first averaged update the average holds the parameters as
+they were when the optimizer bound the arena (its first ``step()`` / ``prepare_capture()``).  Checkpoints carry ``icka_avg`` /
+``icka_avg_n``; a state WITHOUT them (saved by an optimizer that did not average) loaded into an averaging optimizer restarts
+the average: n = 0 and the buffer a copy of the parameters at that moment, so the next averaged update copies the weights.
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes as C
 from typing import List, Optional
 
 import torch
@@ -65,6 +81,26 @@ def schedule_factor(kind: str, warmup: int, total: int, t: int) -> float:
     return max(0.0, float(total - t) / float(max(1, total - warmup)))
 
 
+def average_decay_at(kind: str, decay: float, warmup: bool, n: int) -> float:
+    """The decay the averaged update number n + 1 uses (csrc/optim.hip: optim_average_prepare_kernel), restated in Python:
+    ``avg <- avg + (1 - d) * (p - avg)``.  n == 0 -> 0 (the average starts as a copy of the weights); "swa" -> n / (n + 1)
+    (the equal-weight mean of the n + 1 snapshots); "ema" -> ``decay``, with ``warmup`` min(decay, (1 + n) / (10 + n))."""
+    if kind not in ("ema", "swa"):
+        raise ValueError("average kind %r: 'ema' or 'swa'" % (kind,))
+    if n < 0:
+        raise ValueError("average_decay_at: n must be >= 0")
+    if n == 0:
+        return 0.0
+    if kind == "swa":
+        return float(n) / float(n + 1)
+    return min(float(decay), float(1 + n) / float(10 + n)) if warmup else float(decay)
+
+
+def average_applies(start: int, every: int, t: int) -> bool:
+    """Whether update number t (1-based) is averaged: the first ``start`` updates are not, then every ``every``-th one is."""
+    return t > start and (t - start - 1) % every == 0
+
+
 def _parse_schedule(schedule):
     if schedule is None or schedule == "constant":
         return ("constant", 0, 0)
@@ -79,7 +115,8 @@ def _parse_schedule(schedule):
 class ArenaAdamW(torch.optim.Optimizer):
     def __init__(self, model: torch.nn.Module, params=None, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01, max_grad_norm: Optional[float] = None, capturable: bool = False, schedule=None,
-                 skip_nonfinite: bool = True):
+                 skip_nonfinite: bool = True, average: Optional[str] = None, average_decay: float = 0.999,
+                 average_warmup: bool = True, average_start: int = 0, average_every: int = 1):
         """``model``: the module whose forward built (or will build) the ParamArena.  ``params``: parameters or param groups
         (default: ``reference_param_groups(model, weight_decay)``).  ``max_grad_norm``: clip the global gradient norm inside
         ``step()`` (the reference's clip_grad_norm_(..., 1.0)); None = no clipping.
@@ -90,7 +127,19 @@ class ArenaAdamW(torch.optim.Optimizer):
         of the device schedule.  Host edits of ``lr`` / ``betas`` / ``eps`` / ``weight_decay`` reach the device at the next
         ``step()`` made outside a capture, or at once with ``sync_hyperparameters()``.  ``grad_norm()`` stays a device scalar;
         ``current_lr()``, ``steps_taken()`` and ``skipped_steps()`` read the device block and are the only calls that
-        synchronise.  Before capturing ``step()`` by hand, call ``prepare_capture()`` once with the gradients in place."""
+        synchronise.  Before capturing ``step()`` by hand, call ``prepare_capture()`` once with the gradients in place.
+
+        ``average="ema"`` / ``"swa"`` (module docstring; None: nothing is allocated or launched): keep an averaged copy of the
+        weights of every parameter in the groups.  ``average_decay`` in [0, 1) and ``average_warmup`` belong to the EMA;
+        the first ``average_start`` updates are not averaged, after them every ``average_every``-th one is."""
+        if average not in (None, "ema", "swa"):
+            raise ValueError("ArenaAdamW(average=): None, 'ema' or 'swa', got %r" % (average,))
+        if not 0.0 <= float(average_decay) < 1.0:
+            raise ValueError("ArenaAdamW(average_decay=): in [0, 1), got %r" % (average_decay,))
+        if int(average_start) != average_start or average_start < 0:
+            raise ValueError("ArenaAdamW(average_start=): a non-negative integer, got %r" % (average_start,))
+        if int(average_every) != average_every or average_every < 1:
+            raise ValueError("ArenaAdamW(average_every=): a positive integer, got %r" % (average_every,))
         if params is None:
             params = reference_param_groups(model, weight_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -118,6 +167,14 @@ class ArenaAdamW(torch.optim.Optimizer):
         self._partials = None
         self._clip = None
         self._pending = None     # state loaded before the arena was bound
+        self.average = average
+        self.average_decay, self.average_warmup = float(average_decay), bool(average_warmup)
+        self.average_start, self.average_every = int(average_start), int(average_every)
+        self._avg = None         # average=: f32 buffer of the arena's layout
+        self._avg_table = None   # average=: chunk table over every parameter of the groups, built once per arena
+        self._avg_state = None   # average=, capturable: the icka_average_state block; n lives there once bound
+        self._avg_n = 0          # averaged updates so far (host mode; capturable: what waits for the block)
+        self._swapped = False    # averaged_weights() is active: parameters and average are exchanged
 
     # ------------------------------------------------------------------------------------------------------------
     def _bind(self) -> ParamArena:
@@ -141,10 +198,39 @@ class ArenaAdamW(torch.optim.Optimizer):
                 self._uploaded = None
                 self._table_cache = {}
                 self._write_t(self._t)
+            if self.average is not None:
+                self._bind_average(A)
             if self._pending is not None:       # a state loaded before the arena existed
                 self._install(A, self._pending)
                 self._pending = None
         return A
+
+    def _bind_average(self, A: ParamArena) -> None:
+        """The average buffer (a copy of the parameters), its chunk table over every parameter of the groups -- with or
+        without a gradient: the average of a parameter that does not change is that parameter -- and, capturable, the block."""
+        ranges = []
+        for gi, group in enumerate(self.param_groups):
+            for p in group["params"]:
+                s = A.slots.get(id(p))
+                if s is None:
+                    raise RuntimeError("ArenaAdamW: a parameter of group %d is not in the model's arena" % gi)
+                ranges.append((s.off, s.off + (s.numel + 7) // 8 * 8))
+        merged = []
+        for lo, hi in sorted(ranges):
+            if merged and merged[-1][1] == lo:
+                merged[-1] = (merged[-1][0], hi)
+            else:
+                merged.append((lo, hi))
+        self._avg_table = K.dp_chunk_table(merged, A.device)
+        self._avg = A.flat.detach().clone()
+        if self.capturable:
+            self._avg_state = K.average_state_new(A.device)
+            h = _lib.AverageState()
+            h.n = int(self._avg_n)
+            h.kind = _lib.AVERAGE_SWA if self.average == "swa" else _lib.AVERAGE_EMA
+            h.warmup, h.decay = int(self.average_warmup), self.average_decay
+            h.start, h.every = self.average_start, self.average_every
+            K.average_state_write(self._avg_state, h, 0, C.sizeof(_lib.AverageState))
 
     # ------------------------------------------------------------------------------------------------------------ checkpoints
     @staticmethod
@@ -159,10 +245,22 @@ class ArenaAdamW(torch.optim.Optimizer):
         elif self._pending is not None:
             sd["icka_m"], sd["icka_v"], sd["icka_layout"] = self._pending["icka_m"], self._pending["icka_v"], self._pending["icka_layout"]
         sd["icka_t"] = self.steps_taken() if self._state is not None else int(self._t)
+        if self.average is not None:
+            if self._swapped:
+                raise RuntimeError("ArenaAdamW.state_dict: the averaged weights are swapped in (leave averaged_weights() first)")
+            if self._avg is not None:
+                sd["icka_avg"], sd["icka_avg_n"] = self._avg.detach().cpu().clone(), self.average_count()
+            elif self._pending is not None and "icka_avg" in self._pending:
+                sd["icka_avg"], sd["icka_avg_n"] = self._pending["icka_avg"], int(self._pending["icka_avg_n"])
         return sd
 
     def load_state_dict(self, state_dict):
-        extra = {k: state_dict[k] for k in ("icka_m", "icka_v", "icka_layout", "icka_t") if k in state_dict}
+        if self._swapped:
+            raise RuntimeError("ArenaAdamW.load_state_dict: the averaged weights are swapped in (leave averaged_weights() first)")
+        keys = ("icka_m", "icka_v", "icka_layout", "icka_t") + (("icka_avg", "icka_avg_n") if self.average is not None else ())
+        extra = {k: state_dict[k] for k in keys if k in state_dict}
+        if ("icka_avg" in extra) != ("icka_avg_n" in extra) or ("icka_avg" in extra and "icka_layout" not in extra):
+            raise ValueError("ArenaAdamW.load_state_dict: 'icka_avg', 'icka_avg_n' and 'icka_layout' come together")
         if "icka_t" not in extra:
             raise ValueError("ArenaAdamW.load_state_dict: no 'icka_t' -- not a state_dict of this class (moments and step count "
                              "would silently restart)")
@@ -175,13 +273,28 @@ class ArenaAdamW(torch.optim.Optimizer):
                 self._install(self._arena, extra)
             else:
                 self._pending = extra          # installed when the arena is bound (first step)
+        if self.average is not None and "icka_avg" not in extra:
+            # a state without an average: it restarts from the parameters as they are now (when bound: copied here; else at _bind)
+            self._write_avg_n(0)
+            if self._avg is not None:
+                self._avg.copy_(self._arena.flat)
 
     def _install(self, A: ParamArena, extra) -> None:
         if list(map(tuple, extra["icka_layout"])) != self._layout(A):
             raise ValueError("ArenaAdamW.load_state_dict: the saved moments belong to another parameter layout (different model "
                              "or registration order)")
+        if "icka_avg" in extra and (self._avg is None or tuple(extra["icka_avg"].shape) != tuple(self._avg.shape)):
+            raise ValueError("ArenaAdamW.load_state_dict: the saved average belongs to another parameter layout")
         self._m.copy_(extra["icka_m"])
         self._v.copy_(extra["icka_v"])
+        if "icka_avg" in extra:
+            self._avg.copy_(extra["icka_avg"])
+            self._write_avg_n(int(extra["icka_avg_n"]))
+
+    def _write_avg_n(self, n: int) -> None:
+        self._avg_n = int(n)
+        if self._avg_state is not None:
+            self._avg_state[0:8].view(torch.int64).copy_(torch.tensor([int(n)], dtype=torch.int64))
 
     def _build(self, A: ParamArena):
         """Chunk tables: one per param group over the slots that hold a gradient this step, one over all of them."""
@@ -292,9 +405,15 @@ class ArenaAdamW(torch.optim.Optimizer):
         K.optim_prepare(self._partials, n, float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0, self._state,
                         dry=self._dry, guard=self.skip_nonfinite)
         K.optim_adamw_dev(A.flat, A.gflat, self._m, self._v, A.shadow, A.shadow16, self._table3, self._state)
+        if self.average is not None:
+            K.optim_average_prepare(self._avg_state, self._state)
+            K.optim_average_dev(A.flat, self._avg, self._avg_table, self._avg_state)
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self._swapped:
+            raise RuntimeError("ArenaAdamW.step: the averaged weights are swapped in (averaged_weights() is active); an update "
+                               "now would train the average and average the trained weights")
         loss = closure() if closure is not None else None
         if self.capturable and self._uploaded is None and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("ArenaAdamW(capturable=True): call prepare_capture() (or one step()) before capturing step()")
@@ -325,8 +444,68 @@ class ArenaAdamW(torch.optim.Optimizer):
             K.check(lib.icka_optim_adamw(A.flat.data_ptr(), A.gflat.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), sh, sh16,
                                          table.data_ptr(), table.shape[0], coef, float(group["lr"]), float(b1), float(b2),
                                          float(group["eps"]), float(group["weight_decay"]), self._t, st), "icka_optim_adamw")
+        if self.average is not None and average_applies(self.average_start, self.average_every, self._t):
+            K.optim_average(A.flat, self._avg, self._avg_table,
+                            average_decay_at(self.average, self.average_decay, self.average_warmup, self._avg_n))
+            self._avg_n += 1
         self._mark_shadows_fresh(A)
         return loss
+
+    # ------------------------------------------------------------------------------------------------------------ averaged weights
+    def _need_average(self, what: str) -> ParamArena:
+        if self.average is None:
+            raise RuntimeError("ArenaAdamW.%s belongs to average='ema' / 'swa'" % what)
+        return self._bind()
+
+    def average_count(self) -> int:
+        """Averaged updates so far (n of the device block in capturable mode: synchronises; host mode: the host counter)."""
+        if self.average is None:
+            raise RuntimeError("ArenaAdamW.average_count() belongs to average='ema' / 'swa'")
+        if self._avg_state is None:       # host mode, or not bound yet (a loaded count waits on the host)
+            return int(self._pending["icka_avg_n"]) if self._pending is not None and "icka_avg_n" in self._pending \
+                else int(self._avg_n)
+        return int(K.average_state_read(self._avg_state).n)
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the context the model runs on the averaged weights: parameters and average are exchanged in place (one
+        launch, which also writes the 16-bit shadows), so ``model.state_dict()``, eager forwards and graphs captured earlier
+        all see them; on exit -- also after an exception -- they are exchanged back, bit for bit.  No re-cast is triggered
+        under the "tracked" shadow policy.  ``step()`` / ``TrainStep.__call__`` raise inside it; it does not nest.  What follows
+        the swap is the arena (masters and shadows); a weight copy a module derives for itself outside the arena -- the image
+        encoder's GEMM-layout convolution weights (``icka_amd.resnet``) -- does not: keep such a module out of the groups (the
+        reference's loop leaves its ResNet frozen)."""
+        A = self._need_average("averaged_weights()")
+        if self._swapped:
+            raise RuntimeError("ArenaAdamW.averaged_weights(): already active (the context does not nest)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ArenaAdamW.averaged_weights(): not inside a capture")
+        K.optim_swap(A.flat, self._avg, A.shadow, A.shadow16, self._avg_table)
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            K.optim_swap(A.flat, self._avg, A.shadow, A.shadow16, self._avg_table)
+            self._swapped = False
+
+    @torch.no_grad()
+    def averaged_state_dict(self):
+        """The averaged weights keyed like ``model.state_dict()`` (fresh tensors on the parameters' device).  Parameters that
+        are in no group, and buffers, are passed through as the model holds them.  Does not swap."""
+        A = self._need_average("averaged_state_dict()")
+        avg = A.flat if self._swapped else self._avg      # (while swapped, the arena holds the average)
+        mine = {id(p) for g in self.param_groups for p in g["params"]}
+        sd = self.model.state_dict()
+        named = dict(self.model.named_parameters(remove_duplicate=False))
+        out = type(sd)()
+        for k, v in sd.items():
+            p = named.get(k)
+            s = A.slots.get(id(p)) if p is not None else None
+            if s is not None and id(p) in mine:
+                out[k] = avg[s.off:s.off + s.numel].view(s.shape).clone()
+            else:
+                out[k] = v.detach().clone()
+        return out
 
     @staticmethod
     def _mark_shadows_fresh(A: ParamArena) -> None:

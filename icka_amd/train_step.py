@@ -30,6 +30,9 @@ behind the k-th micro-batch:
   * Construction leaves no trace: the warm-up steps run the update launches DRY (the prepare launch sets the skip word and
     changes nothing else, so parameters, moments, t and the skipped count are never written), and the gradients the caller
     holds are put aside and restored (``graph._GradSnapshot``).  The captures themselves execute nothing.
+  * ``ArenaAdamW(average="ema" | "swa")``: the averaging launches follow the update inside ``optimizer.step()``, so they are
+    nodes of the update graph and nothing changes here; the dry warm-up leaves the average and its count untouched.  While
+    ``optimizer.averaged_weights()`` is active a call raises (a replay could not check it: it runs no Python).
 
 Data parallel (a ``GradReducer`` on the arena) is refused: exchanging or sharding the update inside the graph is out of scope.
 """
@@ -153,6 +156,9 @@ class TrainStep(_StepBase):
     def __call__(self, *args, **kwargs) -> torch.Tensor:
         if self._graphs is None:
             raise RuntimeError("TrainStep is closed")
+        if self.optimizer._swapped:      # (a replay runs no Python: optimizer.step()'s own refusal would never be reached)
+            raise RuntimeError("TrainStep: the optimizer's averaged weights are swapped in (averaged_weights() is active); a "
+                               "training step now would train the average")
         values = self._values(args, kwargs)
         last = self._pos == self.k - 1
         if self._replayable(values) and not _maps_active():   # (attention maps are recorded from eager launches)

@@ -46,7 +46,9 @@ extern "C" {
  *    those setters switched on left the library (profiles/NEGATIVE_RESULTS.md); icka_gemm_ln, icka_gemm_ln_sync_words, icka_gemm_ln_test_hooks, icka_gemm_qkv_attn (additive).
  *    Later, still 6: icka_contrastive_fwd, icka_contrastive_bwd, icka_contrastive_workspace_floats, icka_relu_bwd,
  *    icka_sample_swap (additive: the auxiliary objective of the gated taggers, csrc/objective.hip); icka_optim_prepare,
- *    icka_optim_adamw_dev and the icka_optim_state block (additive: the capturable parameter update). */
+ *    icka_optim_adamw_dev and the icka_optim_state block (additive: the capturable parameter update); icka_optim_average,
+ *    icka_optim_average_prepare, icka_optim_average_dev, icka_optim_swap and the icka_average_state block (additive: EMA / SWA
+ *    weight averaging). */
 #define ICKA_ABI_VERSION 6
 int icka_abi_version(void);
 const char* icka_build_arch(void);
@@ -1188,6 +1190,48 @@ typedef struct icka_optim_state {
 int icka_optim_prepare(const float* partials, int32_t n, float max_norm, int32_t flags, void* state, void* stream);
 int icka_optim_adamw_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, void* shadow_f16,
                          const int64_t* table3_dev, int32_t n_chunks, const void* state, void* stream);
+
+/* An averaged copy of the weights beside the update (icka_amd/optim.py: ArenaAdamW(average="ema" | "swa")): one more f32
+ * buffer of the parameters' layout, one table-driven launch behind the update, and an in-place exchange that leaves every
+ * address a captured graph holds valid.  Added under ABI version 6 (additive).  Chunk tables as for icka_optim_adamw (int64
+ * pairs {first element, count}, counts multiples of 8, at most icka_optim_chunk_elems()); elements in no chunk are never read
+ * or written.
+ *   icka_optim_average:  avg <- avg + (1 - decay) * (params - avg) per element, in f32; decay == 0 copies params bit for bit
+ *                        (the first averaged update).
+ * The capturable form keeps the count of averaged updates and this update's decay in a device block of this layout (8-byte
+ * aligned); "device" fields are written by icka_optim_average_prepare only, "host" fields by the caller outside a capture:
+ *   n                   device  averaged updates so far (the host writes it on resume)
+ *   decay_now, apply    device  what the averaging launch behind this prepare uses; apply == 0: it touches no memory
+ *   kind, warmup        host    ICKA_AVERAGE_EMA / ICKA_AVERAGE_SWA; EMA: 1 = the decay is warmed up
+ *   decay               host    EMA decay in [0, 1)
+ *   start, every        host    update number t (1-based, icka_optim_state.t after its prepare) is averaged iff t > start and
+ *                               (t - start - 1) % every == 0 */
+#define ICKA_AVERAGE_EMA 0
+#define ICKA_AVERAGE_SWA 1
+typedef struct icka_average_state {
+    int64_t n;
+    float decay_now;
+    int32_t apply;
+    int32_t kind;
+    int32_t warmup;
+    double decay;
+    int64_t start;
+    int64_t every;
+} icka_average_state;
+/*   icka_optim_average_prepare: one thread, after icka_optim_prepare.  optim_state->skip set (a dry warm-up launch, a refused
+ *                        non-finite update): apply = 0, nothing else changes.  Otherwise apply as above from optim_state->t;
+ *                        when applying, decay_now = (float) of, in double: 0 if n == 0; n / (n + 1) for SWA; for EMA
+ *                        min(decay, (1 + n) / (10 + n)) with warm-up, else decay; then n += 1.
+ *   icka_optim_average_dev: icka_optim_average's arithmetic with decay_now read from the block; every block reads apply first.
+ *   icka_optim_swap:     exchanges params and avg element by element and writes the bf16 (and fp16, when given) shadow of the
+ *                        new params as icka_optim_adamw writes them (same rounding, same +-65504 clamp).  Applied twice it
+ *                        restores every buffer bit for bit. */
+int icka_optim_average(const float* params, float* avg, const int64_t* table_dev, int32_t n_chunks, float decay, void* stream);
+int icka_optim_average_prepare(void* average_state, const void* optim_state, void* stream);
+int icka_optim_average_dev(const float* params, float* avg, const int64_t* table_dev, int32_t n_chunks, const void* average_state,
+                           void* stream);
+int icka_optim_swap(float* params, float* avg, void* shadow_bf16, void* shadow_f16, const int64_t* table_dev, int32_t n_chunks,
+                    void* stream);
 
 #ifdef __cplusplus
 }
