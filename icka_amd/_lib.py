@@ -127,6 +127,14 @@ PROTOTYPES = {
                                c_i32, c_i32, c_i32, c_f32, c_f32, c_u64, c_vp]),
     "icka_embed_fwd_h": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
                                c_i32, c_i32, c_i32, c_f32, c_f32, c_u64, c_vp]),
+    "icka_embed_fwd_adv": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                                   c_i32, c_i32, c_i32, c_f32, c_f32, c_u64, c_vp]),
+    "icka_embed_fwd_adv_h": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                                     c_i32, c_i32, c_i32, c_f32, c_f32, c_u64, c_vp]),
+    "icka_adv_workspace_floats": (c_i64, [c_i32, c_i32, c_i32]),
+    "icka_adv_ascend": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp]),
+    "icka_adv_init_uniform": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_u64, c_vp, c_vp]),
+    "icka_adv_bump": (c_i32, [c_vp, c_vp]),
     "icka_embed_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
                                c_i32, c_i32, c_i32, c_i32, c_f32, c_u64, c_i32, c_vp]),
     "icka_embed_bwd_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,

@@ -311,10 +311,14 @@ struct EmbFwdArgs {
     // src[t] < 0, prompt vector -1-src[t] of this sample's [P,H] bf16 prompt block; position row = t + pos_offset
     const int32_t* src; const bf16_t* prompt; int S_in, P, pos_offset;
     int yf_f16;   // twin output is fp16 ("mixed16") instead of f32
+    // adversarial forward (icka_embed_fwd_adv, ADV instances only): f32 [M, H] perturbation added to the word row first
+    const float* delta;
 };
 
-template <int NCH>
-__global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbFwdArgs a_) {
+// ADV: s = ((word + delta) + pos) + type, a compile-time instance of its own (embed_fwd_adv_kernel): the plain instances keep
+// their arithmetic and their registers.
+template <int NCH, bool ADV>
+__device__ __forceinline__ void embed_fwd_body(const EmbFwdArgs& a_) {
     EmbFwdArgs a = a_;
     a.drop = drop_resolve(a.drop);
     const int lane = threadIdx.x & 63;
@@ -340,6 +344,12 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbFwdArgs a_) {
                 else load8f(a.word + id * a.H + c * 8, w);
                 load8f(a.pos + (int64_t)(sp + a.pos_offset) * a.H + c * 8, p);
                 load8f(a.type + t * a.H + c * 8, ty);
+                if constexpr (ADV) {
+                    float dl[8];
+                    load8f(a.delta + (int64_t)row * a.H + c * 8, dl);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) w[e] += dl[e];
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { s[i][e] = (w[e] + p[e]) + ty[e]; sum += s[i][e]; }
             } else {
@@ -377,6 +387,10 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbFwdArgs a_) {
         }
     }
 }
+template <int NCH>
+__global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbFwdArgs a) { embed_fwd_body<NCH, false>(a); }
+template <int NCH>
+__global__ __launch_bounds__(256) void embed_fwd_adv_kernel(const EmbFwdArgs a) { embed_fwd_body<NCH, true>(a); }
 
 struct EmbBwdArgs {
     const bf16_t* dy; const int64_t* ids; const int64_t* tt; const bf16_t* xhat; const float* rstd;
@@ -765,17 +779,22 @@ extern "C" int icka_ln_bwd_slabs_live(const void* dy, int64_t lddy, const void* 
 static int embed_fwd_impl(int32_t twin_f16, const int64_t* ids, const int64_t* token_type, const float* word, const float* pos,
                               const float* type, const float* gamma, const float* beta, void* y, void* y_twin,
                               void* xhat, float* rstd, int32_t B, int32_t S, int32_t H, int32_t vocab,
-                              int32_t n_type, float eps, float p_drop, uint64_t seed, void* stream) {
+                              int32_t n_type, float eps, float p_drop, uint64_t seed, void* stream,
+                              const float* delta = nullptr) {
     if (!ids || !word || !pos || !type || !gamma || !beta || !y) return ICKA_E_ARG;
     if (B <= 0 || S <= 0 || H <= 0 || H % 8 != 0 || H > 8 * 64 * MAX_CH || vocab <= 0 || n_type <= 0)
         return ICKA_E_SHAPE;
     if (!al16(word) || !al16(pos) || !al16(type) || !al16(gamma) || !al16(beta) || !al16(y) || (xhat && !al16(xhat)) ||
-        (y_twin && !al16(y_twin)))
+        (y_twin && !al16(y_twin)) || (delta && !al16(delta)))
         return ICKA_E_ALIGN;
     EmbFwdArgs a{ids, token_type, word, pos, type, gamma, beta, (bf16_t*)y, y_twin, (bf16_t*)xhat, rstd,
-                 B * S, S, H, vocab, n_type, eps, make_drop(p_drop, seed), nullptr, nullptr, S, 0, 0, twin_f16};
+                 B * S, S, H, vocab, n_type, eps, make_drop(p_drop, seed), nullptr, nullptr, S, 0, 0, twin_f16, delta};
     hipStream_t st = (hipStream_t)stream;
-    DISPATCH_NCH(pick_nch(H), embed_fwd_kernel, row_grid(B * S), 0, st, a);
+    if (delta) {
+        DISPATCH_NCH(pick_nch(H), embed_fwd_adv_kernel, row_grid(B * S), 0, st, a);
+    } else {   // no perturbation: the launch of icka_embed_fwd itself
+        DISPATCH_NCH(pick_nch(H), embed_fwd_kernel, row_grid(B * S), 0, st, a);
+    }
     ICKA_CHECK_LAUNCH();
     return 0;
 }
@@ -794,6 +813,23 @@ extern "C" int icka_embed_fwd_h(const int64_t* ids, const int64_t* token_type, c
                                 int32_t n_type, float eps, float p_drop, uint64_t seed, void* stream) {
     return embed_fwd_impl(1, ids, token_type, word, pos, type, gamma, beta, y, y_f16, xhat, rstd, B, S, H, vocab, n_type, eps,
                           p_drop, seed, stream);
+}
+
+// Adversarial forward (icka_hip.h, "adversarial training"): icka_embed_fwd / _h with the f32 [B*S, H] perturbation ``delta`` added
+// to the word row before the position and type rows; delta == NULL is icka_embed_fwd / _h itself, launch and bits.
+extern "C" int icka_embed_fwd_adv(const int64_t* ids, const int64_t* token_type, const float* word, const float* pos,
+                                  const float* type, const float* gamma, const float* beta, const float* delta, void* y,
+                                  float* y_f32, void* xhat, float* rstd, int32_t B, int32_t S, int32_t H, int32_t vocab,
+                                  int32_t n_type, float eps, float p_drop, uint64_t seed, void* stream) {
+    return embed_fwd_impl(0, ids, token_type, word, pos, type, gamma, beta, y, y_f32, xhat, rstd, B, S, H, vocab, n_type, eps,
+                          p_drop, seed, stream, delta);
+}
+extern "C" int icka_embed_fwd_adv_h(const int64_t* ids, const int64_t* token_type, const float* word, const float* pos,
+                                    const float* type, const float* gamma, const float* beta, const float* delta, void* y,
+                                    void* y_f16, void* xhat, float* rstd, int32_t B, int32_t S, int32_t H, int32_t vocab,
+                                    int32_t n_type, float eps, float p_drop, uint64_t seed, void* stream) {
+    return embed_fwd_impl(1, ids, token_type, word, pos, type, gamma, beta, y, y_f16, xhat, rstd, B, S, H, vocab, n_type, eps,
+                          p_drop, seed, stream, delta);
 }
 
 // Embeddings of a prompt-spliced sequence (the prompt-accepting encoder stage of the current reference model,

@@ -66,6 +66,7 @@ from . import crf
 from . import kernels as K
 from . import packing
 from .attention_maps import active as _maps_active
+from .adversarial import pass_open as _adv_pass_open
 
 
 def _sig(values) -> tuple:
@@ -961,6 +962,8 @@ class GraphedModule(object):
         if self._caps is None:
             raise RuntimeError("GraphedModule is closed")
         if _maps_active():      # attention maps are recorded from eager launches: no capture, no replay
+            return self._eager(args, kwargs)
+        if _adv_pass_open(self.model):      # an open adversarial pass: the captured forwards hold no perturbation
             return self._eager(args, kwargs)
         kwkeys = tuple(sorted(kwargs))
         kwvalues = [kwargs[k] for k in kwkeys]

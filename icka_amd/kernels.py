@@ -604,6 +604,87 @@ def embed_scatter_rows(rows, ids, dword, *, padding_idx=0, scale=1.0):
           "icka_embed_scatter_rows")
 
 
+# ------------------------------------------------------------------------------------------ adversarial training
+ADV_MAX_H, ADV_MAX_S = 2048, 1024           # limits of icka_adv_ascend / icka_adv_init_uniform (icka_hip.h)
+
+
+def embed_fwd_adv(ids, token_type, word, pos, typ, gamma, beta, delta, y, *, y_f32=None, y_f16=None, xhat=None, rstd=None,
+                  eps=1e-12, p_drop=0.0, seed=0):
+    """embed_fwd with the perturbation ``delta`` (f32 [B, S, H] / [B*S, H] contiguous, or None: embed_fwd itself) added to the
+    word rows (icka_hip.h: icka_embed_fwd_adv / _h)."""
+    lib = _lib.load()
+    _dev(ids, "ids")
+    B, S = ids.shape
+    H = word.shape[1]
+    if y_f32 is not None and y_f16 is not None:
+        raise ValueError("one twin copy: y_f32 or y_f16")
+    twin = y_f16 if y_f16 is not None else y_f32
+    if twin is not None and (twin.dtype != (F16 if y_f16 is not None else F32) or not twin.is_contiguous()):
+        raise ValueError("twin output must be contiguous f32 (y_f32) / fp16 (y_f16)")
+    if delta is not None:
+        _dev(delta, "delta")
+        if delta.dtype != F32 or delta.numel() != B * S * H or not delta.is_contiguous():
+            raise ValueError("delta must be contiguous f32 [B, S, H]")
+    fn = lib.icka_embed_fwd_adv_h if y_f16 is not None else lib.icka_embed_fwd_adv
+    check(fn(ids.data_ptr(), _ptr(token_type), word.data_ptr(), pos.data_ptr(), typ.data_ptr(),
+             gamma.data_ptr(), beta.data_ptr(), _ptr(delta), y.data_ptr(), _ptr(twin), _ptr(xhat), _ptr(rstd),
+             B, S, H, word.shape[0], typ.shape[0], eps, p_drop, seed, _stream()), "icka_embed_fwd_adv")
+    return y
+
+
+def _adv_operands(delta, input_mask):
+    _dev(delta, "delta"); _dev(input_mask, "input_mask")
+    if delta.dtype != F32 or delta.dim() != 3 or not delta.is_contiguous():
+        raise ValueError("delta must be contiguous f32 [B, S, H]")
+    B, S, H = delta.shape
+    if input_mask.dtype != torch.int64 or tuple(input_mask.shape) != (B, S) or not input_mask.is_contiguous():
+        raise ValueError("input_mask must be contiguous int64 [B, S] = %s, got %s %s" % ((B, S), input_mask.dtype, tuple(input_mask.shape)))
+    return B, S, H
+
+
+def adv_workspace_floats(B: int, S: int, H: int) -> int:
+    return int(_lib.load().icka_adv_workspace_floats(B, S, H))
+
+
+def adv_ascend(delta, grad, input_mask, norms, workspace, *, alpha, epsilon):
+    """One ascent step in place on ``delta`` (icka_hip.h: icka_adv_ascend): delta, grad f32 [B, S, H], input_mask int64 [B, S],
+    norms f32 [B, 2], workspace f32 with adv_workspace_floats(B, S, H) elements."""
+    B, S, H = _adv_operands(delta, input_mask)
+    _dev(grad, "grad"); _dev(norms, "norms"); _dev(workspace, "workspace")
+    if grad.dtype != F32 or grad.numel() != delta.numel() or not grad.is_contiguous():
+        raise ValueError("grad must be contiguous f32 with the elements of delta")
+    if norms.dtype != F32 or tuple(norms.shape) != (B, 2) or not norms.is_contiguous():
+        raise ValueError("norms must be contiguous f32 [B, 2]")
+    need = adv_workspace_floats(B, S, H)
+    if need <= 0:
+        raise ValueError("icka_adv_ascend takes H %% 8 == 0, H <= %d, S <= %d; got S = %d, H = %d" % (ADV_MAX_H, ADV_MAX_S, S, H))
+    if workspace.dtype != F32 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError("workspace must be contiguous f32 with at least %d elements" % need)
+    check(_lib.load().icka_adv_ascend(delta.data_ptr(), grad.data_ptr(), input_mask.data_ptr(), norms.data_ptr(), B, S, H,
+                                      float(alpha), float(epsilon), workspace.data_ptr(), _stream()), "icka_adv_ascend")
+    return delta
+
+
+def adv_init_uniform(delta, input_mask, *, epsilon, seed, counter=None):
+    """The uniform start of FreeLB (icka_hip.h: icka_adv_init_uniform); ``counter``: device int64 [1] added to ``seed``, or None."""
+    B, S, H = _adv_operands(delta, input_mask)
+    if counter is not None:
+        _dev(counter, "counter")
+        if counter.dtype != torch.int64 or counter.numel() != 1:
+            raise ValueError("counter must be one device int64")
+    check(_lib.load().icka_adv_init_uniform(delta.data_ptr(), input_mask.data_ptr(), B, S, H, float(epsilon),
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(counter), _stream()), "icka_adv_init_uniform")
+    return delta
+
+
+def adv_bump(counter):
+    """counter[0] += 1 as a one-thread launch (a graph node: every replay of a captured step draws a fresh uniform start)."""
+    _dev(counter, "counter")
+    if counter.dtype != torch.int64 or counter.numel() != 1:
+        raise ValueError("counter must be one device int64")
+    check(_lib.load().icka_adv_bump(counter.data_ptr(), _stream()), "icka_adv_bump")
+
+
 def embed_prompt_fwd(ids, src, prompt, word, pos, typ, gamma, beta, y, *, y_f32=None, xhat=None, rstd=None,
                      pos_offset=0, eps=1e-5, p_drop=0.0, seed=0):
     """Prompt-spliced embeddings + LayerNorm + dropout (icka_hip.h: icka_embed_prompt_fwd).  ids int64 [B,S_in],

@@ -203,6 +203,8 @@ class _LayerNormFn(torch.autograd.Function):
 class BertEmbeddings(_IckaModule):
     """word + position + token_type -> LayerNorm -> dropout (:384-412)."""
 
+    _icka_adv = None      # set by adversarial.Adversary while one of its passes is open on this module
+
     def __init__(self, config):
         super().__init__()
         self.config = config
@@ -221,6 +223,12 @@ class BertEmbeddings(_IckaModule):
         A = self._arena()
         ids = input_ids.contiguous()
         tt = None if token_type_ids is None else token_type_ids.contiguous()
+        adv = self._icka_adv      # an open pass of adversarial.Adversary on this module, else None
+        if adv is not None:
+            adv.check_pass(self, A, B, S)      # the refusals, before any launch
+            d = _dims(self.config, B, S, 0, self.training, mixed=_is_mixed(self))
+            y, yf = ops.EmbeddingsAdvFn.apply(A.anchor, self, A, ids, tt, d, adv)
+            return _with_twin(y, yf, (B, S, -1))
         if _is_exact(self):
             d = _dims(self.config, B, S, 0, self.training, True)
             return X.EmbeddingsFn.apply(A.anchor, self, A, ids, tt, d).view(B, S, -1)

@@ -540,6 +540,51 @@ class EmbeddingsFn(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
+class EmbeddingsAdvFn(torch.autograd.Function):
+    """BertEmbeddings.forward inside a pass of ``adversarial.Adversary``: the forward adds the pass's perturbation (None in a
+    clean pass) to the word rows, the backward leaves THIS pass's per-token word gradient in ``adv.grad`` (overwritten) and
+    folds it into the table gradient.  Position, type and LayerNorm gradients are written as EmbeddingsFn.backward writes them."""
+
+    @staticmethod
+    def forward(ctx, anchor, mod, A: ParamArena, ids, tt, d: Dims, adv):
+        B, S = ids.shape
+        H = d.H
+        save = any(ctx.needs_input_grad)
+        y = torch.empty(B * S, H, dtype=BF16, device=ids.device)
+        yf = torch.empty(B * S, H, dtype=F16 if d.h16 else F32, device=ids.device)
+        xhat = torch.empty_like(y) if save else None
+        rstd = torch.empty(B * S, dtype=F32, device=ids.device) if save else None
+        seed = A.next_seed() if d.p_hidden > 0 else 0
+        K.embed_fwd_adv(ids, tt, mod.word_embeddings.weight, mod.position_embeddings.weight,
+                        mod.token_type_embeddings.weight, mod.LayerNorm.weight, mod.LayerNorm.bias, adv.pass_delta(B, S), y,
+                        xhat=xhat, rstd=rstd, eps=d.eps, p_drop=d.p_hidden, seed=seed,
+                        **({"y_f16": yf} if d.h16 else {"y_f32": yf}))
+        ctx.mod, ctx.A, ctx.d, ctx.seed, ctx.adv = mod, A, d, seed, adv
+        ctx.save_for_backward(ids, tt, xhat, rstd)
+        ctx.mark_non_differentiable(yf)
+        ctx.set_materialize_grads(False)
+        return y, yf
+
+    @staticmethod
+    def backward(ctx, dy, _dyf=None):
+        mod, A, d = ctx.mod, ctx.A, ctx.d
+        ids, tt, xhat, rstd = ctx.saved_tensors
+        dy = _c(dy)
+        ws = A.workspace("ln", K._lib.load().icka_ln_bwd_workspace_floats(d.H))
+        tables = (mod.word_embeddings.weight, mod.position_embeddings.weight)
+        small = (mod.token_type_embeddings.weight, mod.LayerNorm.weight, mod.LayerNorm.bias)
+        if A.grad_beta(tables) == 0.0:   # atomically accumulated tables: fresh gradient starts from zero
+            K.zero_(A.g_cat(tables).view(-1))
+        acc = A.grad_beta(small) > 0
+        dtok = ctx.adv.pass_grad(ids.shape[0], ids.shape[1]).view(ids.numel(), d.H)
+        K.embed_bwd_rows(dy, ids, tt, xhat, rstd, mod.LayerNorm.weight, dtok, A.g(tables[1]), A.g(small[0]), A.g(small[1]),
+                         A.g(small[2]), ws, vocab=tables[0].shape[0], padding_idx=0, p_drop=d.p_hidden, seed=ctx.seed,
+                         accumulate=acc)
+        K.embed_scatter_rows(dtok, ids.reshape(-1), A.g(tables[0]), padding_idx=0, scale=1.0)
+        A.flush_final()
+        return None, None, None, None, None, None, None
+
+
 class BertLayerFn(torch.autograd.Function):
     """BertLayer.forward (:438-442): self-attention block + feed-forward block."""
 

@@ -322,6 +322,61 @@ int icka_embed_prompt_bwd(const void* dy, const int64_t* ids, const int32_t* src
                           int32_t accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Adversarial training on the word embeddings: FGM (Miyato et al. 2017) and FreeLB (Zhu et al. 2020) as a per-token
+ * perturbation (icka_amd/adversarial.py; csrc/adversarial.hip, the forward variant in csrc/layernorm.hip).
+ *
+ * The perturbation is delta f32 [B, S, H], one row per token position, added to the word row before the position and
+ * type rows:
+ *     s[b,t] = ((word[id] + delta[b,t]) + pos[t]) + type[tt],     y = dropout(LayerNorm(s))
+ * A position is valid when input_mask[b,t] != 0 (int64 [B, S]); n_b = number of valid positions of sample b.
+ * Gradient: g[b,t] = dloss / ddelta[b,t] is exactly the row icka_embed_bwd_rows writes to dtok (a zero row for a token
+ * whose clamped id is the padding id).
+ *
+ * icka_embed_fwd_adv / _h: icka_embed_fwd / _h plus a nullable `delta`; with delta == NULL the very launch of
+ * icka_embed_fwd / _h (y, twin, xhat, rstd bitwise).  delta 16-byte aligned, contiguous.
+ *
+ * icka_adv_ascend, one ascent step, in place on delta; per sample b, Frobenius norms over the valid positions only:
+ *   1. n_g = ||g_b||.
+ *   2. If n_g is 0 or not finite (an inf / NaN in g_b, or a sum of squares that overflows f32), delta_b stays as it is
+ *      at the valid positions and is not projected.
+ *   3. Otherwise u = delta_b + (alpha / n_g) g_b.
+ *   4. Projection: if ||u|| > epsilon, u <- u (epsilon / ||u||).
+ *   5. Every non-valid position of delta_b is written as exact 0, whatever it held before.
+ *   6. norms[b] = (n_g, ||delta_b|| after the step) f32 [B, 2]; the second entry is epsilon where step 4 shrank.
+ * Deterministic (no float atomics, fixed summation order: equal inputs give equal bits), three launches, B * ceil(S / 8)
+ * blocks each.  REDUCTION TREE of one sum of squares (the bounds of tests/adversarial_check.py count its depth): a sample
+ * is cut into slabs of 8 token rows, one 256-thread block per slab;
+ *     lane    sequential over its elements: slab rows w, w + 4 (w = wave of the block), per row the chunks lane,
+ *             lane + 64, ... of 8 consecutive floats, element by element               <= 2 * ceil(H / 512) * 8 terms
+ *     wave    four rotate-and-add steps inside rows of 16 lanes, then (l0 + l16) + (l32 + l48)          depth 6
+ *     block   (w0 + w1) + (w2 + w3)                                                                     depth 2
+ *     sample  lane l adds slab partials l and l + 64 (at most 128 slabs), then the wave tree again      depth 1 + 6
+ * The per-slab partials live in `workspace` (icka_adv_workspace_floats(B, S, H) floats: 2 * B * ceil(S / 8)); each later
+ * launch re-reduces them in that fixed order.  Limits: H % 8 == 0, H <= 2048, S <= 1024, B * S * H < 2^32
+ * (ICKA_E_SHAPE beyond; icka_adv_workspace_floats returns 0).
+ *
+ * icka_adv_init_uniform, the uniform start of FreeLB: delta[b,t,h] = r * epsilon / sqrt(n_b * H) at valid positions (f32:
+ * one division, one square root of the exact product, one product), 0 at all others; r in [-1, 1) is
+ * (float)(hash >> 8) * 2^-23 - 1 with hash = icka_hash(s0, s1, flat element index (b S + t) H + h) of csrc/common.h (the
+ * dropout hash) and (s0, s1) the low and high half of seed + counter.  counter_dev: nullable device uint64, added to
+ * `seed` on the device.  icka_adv_bump: a one-thread node that advances the counter by 1 with an ordinary store; queued
+ * after the init launch, every replay of a captured step draws a fresh start while equal (seed, counter) give equal bits. */
+int icka_embed_fwd_adv(const int64_t* ids, const int64_t* token_type, const float* word, const float* pos,
+                       const float* type, const float* gamma, const float* beta, const float* delta, void* y,
+                       float* y_f32, void* xhat, float* rstd, int32_t B, int32_t S, int32_t H, int32_t vocab,
+                       int32_t n_type, float eps, float p_drop, uint64_t seed, void* stream);
+int icka_embed_fwd_adv_h(const int64_t* ids, const int64_t* token_type, const float* word, const float* pos,
+                         const float* type, const float* gamma, const float* beta, const float* delta, void* y,
+                         void* y_f16, void* xhat, float* rstd, int32_t B, int32_t S, int32_t H, int32_t vocab,
+                         int32_t n_type, float eps, float p_drop, uint64_t seed, void* stream);
+int64_t icka_adv_workspace_floats(int32_t B, int32_t S, int32_t H);
+int icka_adv_ascend(float* delta, const float* grad, const int64_t* input_mask, float* norms, int32_t B, int32_t S,
+                    int32_t H, float alpha, float epsilon, float* workspace, void* stream);
+int icka_adv_init_uniform(float* delta, const int64_t* input_mask, int32_t B, int32_t S, int32_t H, float epsilon,
+                          uint64_t seed, const uint64_t* counter_dev, void* stream);
+int icka_adv_bump(uint64_t* counter_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Fused multi-head attention, head size 64 (bert-base 768/12, bert-large 1024/16).
  * BertSelfAttention.forward (:478-506) and BertCoAttention.forward (:590-624):
  *   scores = Q.K^T ; scores *= scale ; scores += add_mask[b, key] ; P = softmax ; P = dropout(P) ; O = P.V
