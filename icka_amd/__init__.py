@@ -26,6 +26,8 @@ from .metrics import ChunkEvaluator
 from .entities import EntityDecoder, NBestEntities
 from . import adversarial
 from .adversarial import Adversary
+from . import sam
+from .sam import SAM
 from .attention_maps import attention_maps   # (the name now denotes the recorder; the module stays importable by its path)
 
 __all__ = ["CRF", "BiLSTM", "set_length_aware", "MTCCMBertForMMTokenClassificationCRF_gate_1", "BertConfig", "BertModel", "BertEmbeddings", "BertEncoder", "BertLayer", "BertLayerNorm", "BertPooler",
@@ -35,4 +37,4 @@ __all__ = ["CRF", "BiLSTM", "set_length_aware", "MTCCMBertForMMTokenClassificati
            "token_ce_loss", "set_precision", "resolved_precision", "ParamArena", "cross_modal", "PromptRobertaModel",
            "GradReducer", "graph", "DevicePrefetcher", "GraphedModule", "GraphedStep", "TrainStep", "packing", "set_packed",
            "PackOverflowError", "TokenBudgetBatchSampler", "metrics", "ChunkEvaluator", "EntityDecoder", "attention_maps",
-           "NBestPaths", "NBestEntities", "ConstrainedPaths", "SampledPaths", "minimum_risk", "adversarial", "Adversary"]
+           "NBestPaths", "NBestEntities", "ConstrainedPaths", "SampledPaths", "minimum_risk", "adversarial", "Adversary", "sam", "SAM"]

@@ -94,6 +94,14 @@ class AverageState(C.Structure):
 
 AverageState.HOST_LO = AverageState.kind.offset
 
+SAM_DRY = 1                                               # flag of icka_sam_prepare
+
+
+class SamState(C.Structure):
+    """Mirror of ``icka_sam_state`` (include/icka_hip.h): the device block of one sharpness-aware ascent, written by
+    icka_sam_prepare only."""
+    _fields_ = [("norm", c_f32), ("scale", c_f32), ("skip", c_i32), ("reserved", c_i32), ("ascents", c_i64), ("skipped", c_i64)]
+
 
 # name -> (restype, argtypes); must list every function declared in include/icka_hip.h
 PROTOTYPES = {
@@ -278,6 +286,10 @@ PROTOTYPES = {
     "icka_optim_average_prepare": (c_i32, [c_vp, c_vp, c_vp]),
     "icka_optim_average_dev": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "icka_optim_swap": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "icka_sam_sqnorm": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "icka_sam_prepare": (c_i32, [c_vp, c_i32, c_f32, c_i32, c_vp, c_vp]),
+    "icka_sam_ascend": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "icka_sam_restore": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     # ---- fp32 "exact" mode (csrc/exact.hip)
     "icka_x_gemm": (c_i32, [C.POINTER(XGemmDesc), c_vp]),
     "icka_x_ln_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_u64,

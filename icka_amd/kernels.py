@@ -1951,6 +1951,84 @@ def optim_swap(flat: torch.Tensor, avg: torch.Tensor, shadow: Optional[torch.Ten
                                       table.shape[0], _stream()), "icka_optim_swap")
 
 
+# ------------------------------------------------------------------------------------------------- sharpness-aware minimisation
+def sam_state_new(device) -> torch.Tensor:
+    """A zeroed ``icka_sam_state`` block (include/icka_hip.h; mirror: _lib.SamState) as a uint8 device tensor."""
+    n = C.sizeof(_lib.SamState)
+    return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device).view(torch.uint8)[:n]
+
+
+def sam_state_read(state: torch.Tensor) -> "_lib.SamState":
+    """The device block as a host structure (one device-to-host copy: synchronises)."""
+    return _lib.SamState.from_buffer_copy(bytes(state.cpu().tolist()))
+
+
+def _sam_operands(what: str, flat, others, shadow, shadow16, table) -> None:
+    """flat: the parameters; others: (name, f32 buffer of the same layout) pairs, none of them the same buffer as another."""
+    bufs = [("params", flat)] + list(others)
+    for n, t in bufs:
+        _dev(t, n)
+        if t.dtype != F32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != flat.numel():
+            raise TypeError("%s: %s must be a contiguous 1-D f32 tensor of the parameters' length" % (what, n))
+    if len({t.data_ptr() for _, t in bufs}) != len(bufs):
+        raise ValueError("%s: %s must be separate buffers" % (what, ", ".join(n for n, _ in bufs)))
+    for n, t, dt in (("shadow", shadow, BF16), ("shadow16", shadow16, F16)):
+        if t is not None:
+            _dev(t, n)
+            if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != flat.numel():
+                raise TypeError("%s: %s must be a contiguous 1-D %s tensor of the parameters' length" % (what, n, dt))
+    _dev(table, "table")
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 2 or not table.is_contiguous():
+        raise TypeError("%s: the chunk table is a contiguous int64 [n, 2] tensor (dp_chunk_table)" % what)
+
+
+def sam_sqnorm(flat: torch.Tensor, gflat: torch.Tensor, table: torch.Tensor, partials: torch.Tensor, adaptive: bool) -> None:
+    """partials[b] = sum over chunk b of (t g)^2, t = 1 or (``adaptive``) |p|; not adaptive: icka_optim_sqnorm's bits."""
+    _sam_operands("sam_sqnorm", flat, [("grads", gflat)], None, None, table)
+    _dev(partials, "partials")
+    if partials.dtype != F32 or not partials.is_contiguous() or partials.numel() < table.shape[0]:
+        raise TypeError("sam_sqnorm: partials must be a contiguous f32 tensor of at least one element per chunk")
+    if table.shape[0] == 0:
+        return
+    check(_lib.load().icka_sam_sqnorm(flat.data_ptr(), gflat.data_ptr(), table.data_ptr(), table.shape[0], int(bool(adaptive)),
+                                      partials.data_ptr(), _stream()), "icka_sam_sqnorm")
+
+
+def sam_prepare(partials: Optional[torch.Tensor], n: int, rho: float, state: torch.Tensor, dry: bool = False) -> None:
+    """Norm, step scale and the skip word of the ascent behind it into the state block; counts the ascent (``dry``: not)."""
+    _state_operand("sam_prepare", state, _lib.SamState)
+    if not float(rho) > 0.0:
+        raise ValueError("sam_prepare: rho must be positive, got %r" % (rho,))
+    if n > 0 and (partials is None or partials.numel() < n):
+        raise ValueError("sam_prepare: %d partials asked for, %s given" % (n, None if partials is None else partials.numel()))
+    check(_lib.load().icka_sam_prepare(_ptr(partials), int(n), float(rho), _lib.SAM_DRY if dry else 0, state.data_ptr(),
+                                       _stream()), "icka_sam_prepare")
+
+
+def sam_ascend(flat: torch.Tensor, gflat: torch.Tensor, backup: torch.Tensor, shadow: Optional[torch.Tensor],
+               shadow16: Optional[torch.Tensor], table: torch.Tensor, state: torch.Tensor, adaptive: bool) -> None:
+    """backup <- flat; flat <- flat + e over the chunks of ``table``, with the 16-bit shadows of the new flat (either may be
+    None); nothing is touched when the block's skip word is set."""
+    _sam_operands("sam_ascend", flat, [("grads", gflat), ("backup", backup)], shadow, shadow16, table)
+    _state_operand("sam_ascend", state, _lib.SamState)
+    if table.shape[0] == 0:
+        return
+    check(_lib.load().icka_sam_ascend(flat.data_ptr(), gflat.data_ptr(), backup.data_ptr(), _ptr(shadow), _ptr(shadow16),
+                                      table.data_ptr(), table.shape[0], int(bool(adaptive)), state.data_ptr(), _stream()),
+          "icka_sam_ascend")
+
+
+def sam_restore(flat: torch.Tensor, backup: torch.Tensor, shadow: Optional[torch.Tensor], shadow16: Optional[torch.Tensor],
+                table: torch.Tensor, state: torch.Tensor) -> None:
+    """flat <- backup over the chunks of ``table``, with the 16-bit shadows; nothing is touched when the skip word is set."""
+    _sam_operands("sam_restore", flat, [("backup", backup)], shadow, shadow16, table)
+    _state_operand("sam_restore", state, _lib.SamState)
+    if table.shape[0] == 0:
+        return
+    check(_lib.load().icka_sam_restore(flat.data_ptr(), backup.data_ptr(), _ptr(shadow), _ptr(shadow16), table.data_ptr(),
+                                       table.shape[0], state.data_ptr(), _stream()), "icka_sam_restore")
+
+
 # ------------------------------------------------------------------------------------------------- per-sample gates
 def sample_gate_fwd(a, c, gate, mode, out, B, S):
     _mat(a, "a"); _mat(out, "out")

@@ -175,6 +175,7 @@ class ArenaAdamW(torch.optim.Optimizer):
         self._avg_state = None   # average=, capturable: the icka_average_state block; n lives there once bound
         self._avg_n = 0          # averaged updates so far (host mode; capturable: what waits for the block)
         self._swapped = False    # averaged_weights() is active: parameters and average are exchanged
+        self._perturbed = False  # a sam.SAM perturbation is in place: the parameters are w + e(w), not w
 
     # ------------------------------------------------------------------------------------------------------------
     def _bind(self) -> ParamArena:
@@ -414,6 +415,9 @@ class ArenaAdamW(torch.optim.Optimizer):
         if self._swapped:
             raise RuntimeError("ArenaAdamW.step: the averaged weights are swapped in (averaged_weights() is active); an update "
                                "now would train the average and average the trained weights")
+        if self._perturbed:
+            raise RuntimeError("ArenaAdamW.step: a sharpness-aware perturbation is in place (SAM.perturbed() is active); an "
+                               "update now would move w + e(w), and the restore would then throw it away")
         loss = closure() if closure is not None else None
         if self.capturable and self._uploaded is None and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("ArenaAdamW(capturable=True): call prepare_capture() (or one step()) before capturing step()")
@@ -480,6 +484,9 @@ class ArenaAdamW(torch.optim.Optimizer):
             raise RuntimeError("ArenaAdamW.averaged_weights(): already active (the context does not nest)")
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("ArenaAdamW.averaged_weights(): not inside a capture")
+        if self._perturbed:
+            raise RuntimeError("ArenaAdamW.averaged_weights(): a sharpness-aware perturbation is in place (SAM.perturbed() is "
+                               "active); its restore would overwrite the averaged weights with the trained ones")
         K.optim_swap(A.flat, self._avg, A.shadow, A.shadow16, self._avg_table)
         self._swapped = True
         try:

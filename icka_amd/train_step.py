@@ -33,6 +33,9 @@ behind the k-th micro-batch:
   * ``ArenaAdamW(average="ema" | "swa")``: the averaging launches follow the update inside ``optimizer.step()``, so they are
     nodes of the update graph and nothing changes here; the dry warm-up leaves the average and its count untouched.  While
     ``optimizer.averaged_weights()`` is active a call raises (a replay could not check it: it runs no Python).
+  * ``sam.SAM``: with ``sam.run`` in ``step_fn`` the clean pass, the ascent, the second pass and the restore are nodes of the
+    same graph, in front of the update; the dry warm-up sets the ascent's skip word, so the weights are never moved and nothing
+    is counted.  k > 1 is refused for a model with a registered ``SAM`` (its perturbation must come from one batch alone).
 
 Data parallel (a ``GradReducer`` on the arena) is refused: exchanging or sharding the update inside the graph is out of scope.
 """
@@ -46,6 +49,7 @@ from . import kernels as K
 from .attention_maps import active as _maps_active
 from .graph import _GradSnapshot, _StepBase, _end_capture_quietly, _sig
 from .optim import ArenaAdamW
+from .sam import registered as _sam_registered
 
 _FIRST, _MID, _LAST = "overwrite", "accumulate", "update"
 
@@ -67,6 +71,10 @@ class TrainStep(_StepBase):
                                       % type(optimizer).__name__)
         if optimizer.model is not model:
             raise ValueError("TrainStep: the optimizer belongs to another model")
+        if accumulate > 1 and _sam_registered(model):
+            raise NotImplementedError("TrainStep(accumulate=%d): a sam.SAM is registered for this model; its first pass would add "
+                                      "a micro-batch to the sum of the earlier ones, and the perturbation must come from one "
+                                      "batch alone (use accumulate=1)" % accumulate)
         arena = getattr(model, "_icka_arena", None)
         if arena is not None and arena.reducer is not None:
             raise NotImplementedError("TrainStep: this model's arena has a GradReducer attached; a data-parallel update inside "

@@ -48,7 +48,8 @@ extern "C" {
  *    icka_sample_swap (additive: the auxiliary objective of the gated taggers, csrc/objective.hip); icka_optim_prepare,
  *    icka_optim_adamw_dev and the icka_optim_state block (additive: the capturable parameter update); icka_optim_average,
  *    icka_optim_average_prepare, icka_optim_average_dev, icka_optim_swap and the icka_average_state block (additive: EMA / SWA
- *    weight averaging). */
+ *    weight averaging); icka_sam_sqnorm, icka_sam_prepare, icka_sam_ascend, icka_sam_restore and the icka_sam_state block
+ *    (additive: sharpness-aware minimisation, csrc/sam.hip). */
 #define ICKA_ABI_VERSION 6
 int icka_abi_version(void);
 const char* icka_build_arch(void);
@@ -1287,6 +1288,47 @@ int icka_optim_average_dev(const float* params, float* avg, const int64_t* table
                            void* stream);
 int icka_optim_swap(float* params, float* avg, void* shadow_bf16, void* shadow_f16, const int64_t* table_dev, int32_t n_chunks,
                     void* stream);
+
+/* Sharpness-aware minimisation on the flat parameter buffers (csrc/sam.hip; icka_amd/sam.py: SAM): the gradient at w, an ascent
+ * to w + e(w), the gradient there, the way back, and the optimizer's update of w with that second gradient (SAM, Foret et al.
+ * 2021; the scale-invariant ASAM, Kwon et al. 2021).  None of it is in the reference, which trains without SAM.  Added under ABI
+ * version 6 (additive).  Chunk tables as for icka_optim_adamw (int64 pairs {first element, count}, counts multiples of 8, at most
+ * icka_optim_chunk_elems()); elements in no chunk are never read or written.  The values of one ascent live in a device block of
+ * this layout (8-byte aligned), written by thread 0 of icka_sam_prepare with ordinary stores and read by the launches behind it
+ * on the stream; the host only ever reads it:
+ *   norm             norm of the first-pass gradient: sqrt(sum of (t g)^2), t = 1 (plain) or |p| (adaptive)
+ *   scale            step scale of this ascent: (float)(rho / ((double)norm + 1e-12)); 0 for a refused one
+ *   skip             1: the ascend and restore launches behind this prepare return without touching memory
+ *   ascents, skipped ascents applied / refused so far (a dry prepare counts as neither) */
+#define ICKA_SAM_DRY 1          /* prepare flag: set skip, change nothing else (warm-up launches ahead of a capture) */
+typedef struct icka_sam_state {
+    float norm;
+    float scale;
+    int32_t skip;
+    int32_t reserved;
+    int64_t ascents;
+    int64_t skipped;
+} icka_sam_state;
+/*   icka_sam_sqnorm:  partials[b] = sum of (t g)^2 over chunk b.  adaptive == 0: icka_optim_sqnorm itself (params is not read and
+ *                     may be NULL; bitwise its partials).  adaptive != 0: the same loop and reduction tree over a = |p| * g.
+ *   icka_sam_prepare: one block.  Sums the n partials in icka_optim_clip's order, in double; norm = (float)sqrt(sum).  A sum that
+ *                     is not finite or is zero: skip = 1, skipped += 1, scale = 0.  Otherwise scale as above, skip = 0,
+ *                     ascents += 1.  rho must be positive.
+ *   icka_sam_ascend:  returns at once when skip is set.  Otherwise per element backup = p and p <- p + e, every operation an f32
+ *                     rounding of its own (no fused multiply-add), in this order: plain e = scale * g (two roundings with the
+ *                     sum); adaptive t = p * p, u = t * g, e = u * scale (four) -- e = p^2 g rho / || |p| g ||, over every
+ *                     element of the table, biases included.  Writes the bf16 (and fp16, when given) shadow of the new p as
+ *                     icka_optim_adamw writes them (same rounding, same +-65504 clamp); either shadow pointer may be NULL.
+ *   icka_sam_restore: returns at once when skip is set.  Otherwise p = backup bit for bit, and the shadows of p.  (Not p - e:
+ *                     the weights after a step are then bitwise what the optimizer left, and a NaN that reached the
+ *                     perturbation cannot survive it.) */
+int icka_sam_sqnorm(const float* params, const float* grads, const int64_t* table_dev, int32_t n_chunks, int32_t adaptive,
+                    float* partials, void* stream);
+int icka_sam_prepare(const float* partials, int32_t n, float rho, int32_t flags, void* state, void* stream);
+int icka_sam_ascend(float* params, const float* grads, float* backup, void* shadow_bf16, void* shadow_f16, const int64_t* table_dev,
+                    int32_t n_chunks, int32_t adaptive, const void* state, void* stream);
+int icka_sam_restore(float* params, const float* backup, void* shadow_bf16, void* shadow_f16, const int64_t* table_dev,
+                     int32_t n_chunks, const void* state, void* stream);
 
 #ifdef __cplusplus
 }
